@@ -13,9 +13,13 @@ SearchForTriangulationRaw, src/cORBmatcher.cpp:968-1156).
 Multi-GPU (torchrun, one process per GPU): every rank runs the same step on its own
 segment of multi-frames (independent units -> weak scaling, no data-path collective);
 the timed region is bracketed by barrier + synchronize and the max over ranks is taken.
-Side legs in the same JSON line: LocalBA (config C, replicas), GlobalBA (config E, points
-sharded, RCCL all-reduce per LM trial) and config D (8 cams 1024^2, camera per GPU, RCCL
-all-gather of the per-camera blocks).
+
+A plain run sets up, warms up, times `--steps` steps, writes the last timed step's outputs when
+`--dump-outputs DIR` is given, and prints the headline figure.  `--full` adds everything else to
+the same JSON line: the stage-timed steps and rooflines, the single multi-frame latency, the side
+legs LocalBA (config C, replicas), GlobalBA (config E, points sharded, RCCL all-reduce per LM
+trial), config D (8 cams 1024^2, camera per GPU, RCCL all-gather of the per-camera blocks), BoW
+and triangulation, the CPU baselines and the bit-exact parity check against the oracle.
 
 Prints ONE JSON line (rank 0).
 """
@@ -285,6 +289,44 @@ def check_against_cpu_baseline(ref, d_kps, d_cnt, d_desc, d_m, ncams, of_step="l
     return {"camera_frames_bitexact": len(frames), "match_pairs_bitexact": npairs,
             "keypoints_checked": int(sum(len(k) for row in kpss for k in row)),
             "of_step": of_step}
+
+
+DUMP_BUDGET_BYTES = 48 << 20   # of the 64 MB a dump may take
+
+
+def dump_outputs(out_dir, d_kps, d_cnt, d_desc, d_m, pairs):
+    """`--dump-outputs DIR`: what a caller of the timed step receives, from its last run, as
+    float32 DIR/<name>.npy: the keypoint count of every camera-frame, and for a fixed (seed 0)
+    sample of camera-frames and of match pairs the keypoint records, the descriptors and the
+    four top-2 match arrays.  Rows past a frame's count are not part of the result and are
+    written as zero.  The sample is a function of the shapes alone, so two builds run with the
+    same arguments write comparable files."""
+    import mcs_amd
+    os.makedirs(out_dir, exist_ok=True)
+    F, cap = d_desc.shape[0], d_desc.shape[1]
+    NP = len(pairs)
+    per_item = cap * 4 * (7 + d_desc.shape[2] + len(d_m))     # one frame + one pair, as float32
+    n = max(1, DUMP_BUDGET_BYTES // per_item)
+    rng = np.random.default_rng(0)
+    fsel = np.sort(rng.choice(F, min(F, n), replace=False))
+    psel = np.sort(rng.choice(NP, min(NP, n), replace=False)) if NP else np.zeros(0, np.int64)
+    cnt = d_cnt.cpu().numpy()
+    kp = d_kps.cpu().numpy().view(mcs_amd.KEYPOINT_DTYPE).reshape(F, cap)[fsel]
+    kpf = np.stack([kp[name].astype(np.float32) for name in mcs_amd.KEYPOINT_DTYPE.names], -1)
+    de = d_desc.cpu().numpy()[fsel].astype(np.float32)
+    row = np.arange(cap)
+    fvalid = row[None, :] < cnt[fsel][:, None]
+    kpf[~fvalid] = 0
+    de[~fvalid] = 0
+    m = np.stack([x.cpu().numpy()[psel] for x in d_m]).astype(np.float32)
+    pvalid = row[None, :] < cnt[pairs.reshape(-1, 2)[psel, 0]][:, None]
+    m[:, ~pvalid] = 0
+    arrays = {"counts": cnt.astype(np.float32), "frame_index": fsel.astype(np.float32),
+              "keypoints": kpf, "descriptors": de, "pair_index": psel.astype(np.float32),
+              "matches": m}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 def single_multiframe_latency(ex, d_img, d_midx, d_kps, d_cnt, d_desc, ncams, stream, reps):
@@ -765,7 +807,19 @@ def main():
                     help="single multi-frame extraction latency samples; 0 = off")
     ap.add_argument("--selftest-dist", action="store_true",
                     help="CPU (gloo) rehearsal of the multi-rank launch and collectives only")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the stage-timed steps and "
+                         "rooflines, latency, LocalBA / GlobalBA / config D / BoW / triangulation "
+                         "legs, the CPU baselines and the parity check against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, print the line; nothing else
+        args.no_cpu_baseline = True
+        args.stage_timing = 0
+        args.ba_calls = args.gba_calls = args.d_multiframes = 0
+        args.bow_reps = args.tri_reps = args.latency_reps = 0
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `bench.py --gpus N` outside torchrun: start N fresh ranks as child processes (nothing
@@ -923,6 +977,9 @@ def main():
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, *bufs[last_b], d_m, pairs)
     # matcher device time (events on the launch stream around the match launch alone): in split
     # mode the timed step's events also wrap the wait on the second half's extraction, so the
     # figure comes from the one-stream stage-timing steps below instead
@@ -939,7 +996,8 @@ def main():
         ex.enable_timing(False)
         match_ms_last = ev_m0.elapsed_time(ev_m1)
 
-    kp_per_step = int(d_cnt.sum().item())
+    # the stage-timed steps wrote output set 0 last; without them the last timed step's set
+    kp_per_step = int((d_cnt if args.stage_timing else bufs[last_b][1]).sum().item())
     dt_max, kp_tot = reduce_over_ranks(dt, kp_per_step * args.steps, dev, world)
     latency = single_multiframe_latency(ex, d_img, d_midx, d_kps, d_cnt, d_desc, NC, stream,
                                         args.latency_reps) if args.latency_reps > 0 else None
@@ -1072,6 +1130,8 @@ def main():
             "latency": latency,
             "stage_ms_per_step": {k: round(v, 4) for k, v in stage_ms.items()},
             "match_ms_per_step": None if match_ms_last is None else round(match_ms_last, 4),
+            "full": bool(args.full),
+            "dumped_outputs": dumped,
         }
         print(json.dumps(out))
     if world > 1:

@@ -3,7 +3,7 @@
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out
 L=multicol-slam-annotation_amd/lib
-ARGS="--steps 5 --warmup 2 --no-cpu-baseline --ba-calls 0 --gba-calls 0 --bow-reps 0 --d-multiframes 0 --latency-reps 0 --tri-reps 0"
+ARGS="--full --steps 5 --warmup 2 --no-cpu-baseline --ba-calls 0 --gba-calls 0 --bow-reps 0 --d-multiframes 0 --latency-reps 0 --tri-reps 0"
 for rep in 1 2; do
   for v in main "$@"; do
     if [ "$v" = main ]; then lib=$L/libmcs_amd.so; else lib=$L/var_$v/libmcs_amd.so; fi

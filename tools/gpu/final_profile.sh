@@ -10,7 +10,7 @@ TAG=${1:-r02}
 O=gpurun_out/fp_$TAG; mkdir -p $O
 # --split 1: every launch covers the whole 513-frame batch on one stream (the bench's stage-timed
 # roofline launches), so per-launch durations, bytes and VALU counts are per step
-ARGS="--steps 5 --warmup 1 --split 1 --pipeline 0 --no-cpu-baseline --ba-calls 0 --gba-calls 0 --d-multiframes 0 --bow-reps 0 --latency-reps 0 --tri-reps 0"
+ARGS="--full --steps 5 --warmup 1 --split 1 --pipeline 0 --no-cpu-baseline --ba-calls 0 --gba-calls 0 --d-multiframes 0 --bow-reps 0 --latency-reps 0 --tri-reps 0"
 # kernel-trace pass: 2 warmup + 5 timed steps (the clocks settle: a pass of one step measured
 # every kernel 7-13 % slower), then the bench's 5 stage-timed steps (stages back to back, the
 # level-0 blur not beside the resize chain), which stage_trace_summary.py picks out

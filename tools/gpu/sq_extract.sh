@@ -4,7 +4,7 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 TAG=${1:-sq}
 OUT=gpurun_out/sq_$TAG; mkdir -p $OUT
-ARGS="--steps 2 --warmup 1 --no-cpu-baseline --ba-calls 0 --gba-calls 0 --d-multiframes 0 --bow-reps 0 --stage-timing 0"
+ARGS="--full --steps 2 --warmup 1 --no-cpu-baseline --ba-calls 0 --gba-calls 0 --d-multiframes 0 --bow-reps 0 --stage-timing 0"
 hipcc --offload-arch=gfx950 -O3 tools/bench/mfma_f64_peak.hip -o tools/bench/mfma_f64_peak && \
   timeout -k 10 60 ./tools/bench/mfma_f64_peak > $OUT/mfma_f64_peak.json || { echo "peak probe failed"; exit 1; }
 cat $OUT/mfma_f64_peak.json
