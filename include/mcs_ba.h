@@ -328,6 +328,23 @@ int mcs_ba_enable_timing(mcs_ba_ctx* c, int32_t on);
 int mcs_ba_read_timing(mcs_ba_ctx* c, double* ms, int32_t* n_iterations, int32_t* n_trials,
                        int32_t* last_n, int32_t reset);
 
+/* Test hook: the reduced camera system of the last mcs_global_ba / mcs_ba_optimize* /
+ * mcs_local_ba* call on this context (its last setup): *n = 6 * active poses, *tiles = its 64 x 64
+ * tile count T, *band = the tile diagonals the factorisation ran on (the band derived from the
+ * point -> pose lists, clamped to [2, T], when the pipelined factorisation ran; T for a dense
+ * factorisation), *pipelined = 1 when the one-launch pipelined factorisation ran (never for
+ * T = 1).  Any pointer may be NULL. */
+int mcs_ba_read_solve_shape(mcs_ba_ctx* c, int32_t* n, int32_t* tiles, int32_t* band, int32_t* pipelined);
+/* Test hook: the factorisation of multi-tile reduced systems on this context.  0 (default): the
+ * banded pipeline where the size allows it (else one panel launch per step).  1: the dense
+ * pipeline (band := T; at most 96 tiles).  2: one panel launch per step (up to 96 tiles with the
+ * multi-workgroup backward substitution, i.e. the pipeline's operations in the pipeline's order;
+ * above with the one-workgroup one; at most 192 tiles).  Only the factorisation changes: a
+ * sharded run exchanges the derived band whatever the mode.  A call whose system the mode does
+ * not take returns MCS_ERR_UNSUPPORTED (no fall-back to another mode).  One-tile systems have one
+ * path and ignore the mode. */
+int mcs_ba_set_ldlt_mode(mcs_ba_ctx* c, int32_t mode);
+
 /* Host wall time of the host-side phases of the calls on this context (always accumulated):
  * 0 argument checks + active counts, 1 structure build (initializeOptimization +
  * buildStructure), 2 packing + upload of the problem, 3 waiting for the device + result

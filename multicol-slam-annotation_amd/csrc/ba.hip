@@ -1643,7 +1643,11 @@ struct mcs_ba_ctx {
   // optional stage timing (mcs_ba_enable_timing): HIP events on st around each stage,
   // accumulated after the per-trial synchronisation the LM control needs anyway
   bool timing = false;
-  bool ldlt_pipe = true;   // pipelined LDL^T for multi-tile systems (2 <= T <= kPipeMaxT)
+  // factorisation of multi-tile systems (mcs_ba_set_ldlt_mode): 0 banded pipeline where the
+  // size allows it, 1 dense pipeline (band := T), 2 one panel launch per step
+  int ldlt_mode = 0;
+  // reduced system of the last setup (mcs_ba_read_solve_shape)
+  int32_t shape_n = 0, shape_T = 0, shape_band = 0, shape_pipe = 0;
   hipEvent_t ev[8] = {};
   double acc_ms[MCS_BA_NSTAGES] = {};
   double host_ms[MCS_BA_NHOST] = {};   // host phases (mcs_ba_read_host_timing)
@@ -1962,12 +1966,24 @@ struct Optimizer {
       band = ldlt::pipe_band(T, (int)wd + 1);
       if (sharded) xs_count = (size_t)ldlt::TB * T + ldlt::band_tiles((int)wd + 1, T) * ldlt::TB * ldlt::TB;
     }
-    const bool pipelined = T >= 2 && c->ldlt_pipe && ldlt::pipe_supported(T, band);
-    if (!pipelined && (size_t)T * ldlt::TB * 8 > 96 * 1024) {
-      set_error("more than 2048 active poses with a reduced camera system too wide for the banded "
-                "factorisation (its task table exceeds the pipeline's bound)");
+    // the forced modes factor densely; the exchange above keeps the derived band
+    if (c->ldlt_mode != 0) band = T;
+    if (c->ldlt_mode == 1 && T >= 2 && !ldlt::pipe_supported(T, T)) {
+      set_error("BA: the dense pipelined factorisation (mcs_ba_set_ldlt_mode 1) takes at most 96 tiles");
       return MCS_ERR_UNSUPPORTED;
     }
+    const bool pipelined = T >= 2 && c->ldlt_mode != 2 && ldlt::pipe_supported(T, band);
+    // mode 2 with the multi-workgroup backward substitution (the pipeline's sync words, no tasks):
+    // the same operations in the same order as the pipeline; above 96 tiles the one-workgroup one
+    const bool per_step_sync = T >= 2 && c->ldlt_mode == 2 && ldlt::pipe_supported(T, T);
+    if (!pipelined && (size_t)T * ldlt::TB * 8 > 96 * 1024) {
+      set_error(c->ldlt_mode == 2
+                    ? "BA: the per-step factorisation (mcs_ba_set_ldlt_mode 2) takes at most 2048 active poses"
+                    : "more than 2048 active poses with a reduced camera system too wide for the banded "
+                      "factorisation (its task table exceeds the pipeline's bound)");
+      return MCS_ERR_UNSUPPORTED;
+    }
+    c->shape_n = n; c->shape_T = T; c->shape_band = pipelined ? band : T; c->shape_pipe = pipelined ? 1 : 0;
     {
       Packer pk;
       if (!split) add_problem(pk, poses, points, &d_poses_bk, &d_points_bk);
@@ -2024,6 +2040,13 @@ struct Optimizer {
     lw.z = dz((size_t)ldlt::TB * T);
     // pipelined factorisation (one launch per solve) for every multi-tile system
     lw.W = nullptr; lw.du = nullptr; lw.sync = nullptr; lw.tasks = nullptr; lw.ntasks = 0; lw.pipe_T = 0;
+    lw.band = 0; lw.per_step = false;
+    if (per_step_sync) {
+      lw.sync = (unsigned*)dz((ldlt::pipe_sync_words(T, T) + 1) / 2);
+      lw.pipe_T = T;
+      lw.band = T;
+      lw.per_step = true;
+    }
     if (pipelined) {
       const std::vector<int4>& tq = ldlt::pipe_tasks_host(T, band);
       lw.W = dz(ldlt::tile_doubles(T));
@@ -2769,6 +2792,21 @@ int mcs_ba_read_timing(mcs_ba_ctx* c, double* ms, int32_t* n_iterations, int32_t
     for (double& v : c->acc_ms) v = 0.0;
     c->n_iter = c->n_trial = 0;
   }
+  return MCS_OK;
+}
+
+int mcs_ba_read_solve_shape(mcs_ba_ctx* c, int32_t* n, int32_t* tiles, int32_t* band, int32_t* pipelined) {
+  if (!c) return MCS_ERR_ARG;
+  if (n) *n = c->shape_n;
+  if (tiles) *tiles = c->shape_T;
+  if (band) *band = c->shape_band;
+  if (pipelined) *pipelined = c->shape_pipe;
+  return MCS_OK;
+}
+
+int mcs_ba_set_ldlt_mode(mcs_ba_ctx* c, int32_t mode) {
+  if (!c || mode < 0 || mode > 2) return MCS_ERR_ARG;
+  c->ldlt_mode = mode;
   return MCS_OK;
 }
 

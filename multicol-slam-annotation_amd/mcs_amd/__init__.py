@@ -136,6 +136,8 @@ SIGNATURES = {
     "mcs_ba_enable_timing": (ctypes.c_int, [_P, _I32]),
     "mcs_ba_read_timing": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32]),
     "mcs_ba_read_host_timing": (ctypes.c_int, [_P, _P, _P, _I32]),
+    "mcs_ba_read_solve_shape": (ctypes.c_int, [_P, _P, _P, _P, _P]),
+    "mcs_ba_set_ldlt_mode": (ctypes.c_int, [_P, _I32]),
     "mcs_ba_check_structure": (ctypes.c_int, [_P, _P, _P]),
     "mcs_distinctive_descriptors_device": (ctypes.c_int, [_P, _P, _I32, _P, _P, _I32, _P, _P, _P, _P]),
     "mcs_update_normal_depth_device": (ctypes.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P]),

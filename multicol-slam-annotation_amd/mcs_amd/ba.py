@@ -962,6 +962,27 @@ def _solver_read_host_timing(self, reset=True):
     return dict(zip(BA_HOST_PHASES, ms.tolist())), n.value
 
 
+LDLT_BANDED, LDLT_DENSE, LDLT_PER_STEP = 0, 1, 2
+
+
+def _solver_read_solve_shape(self):
+    """-> dict(n, T, band, pipelined) of the last call's reduced camera system
+    (mcs_ba_read_solve_shape): band = the tile diagonals the factorisation ran on."""
+    from . import _check
+    v = [ctypes.c_int32() for _ in range(4)]
+    _check(self._lib.mcs_ba_read_solve_shape(self._h, *[ctypes.byref(x) for x in v]))
+    return dict(n=v[0].value, T=v[1].value, band=v[2].value, pipelined=bool(v[3].value))
+
+
+def _solver_set_ldlt_mode(self, mode):
+    """Test hook (mcs_ba_set_ldlt_mode): 0 banded pipeline (default), 1 dense pipeline,
+    2 one panel launch per step.  A later call the mode does not take raises McsError."""
+    from . import _check
+    _check(self._lib.mcs_ba_set_ldlt_mode(self._h, int(mode)))
+
+
+Solver.read_solve_shape = _solver_read_solve_shape
+Solver.set_ldlt_mode = _solver_set_ldlt_mode
 Solver.read_host_timing = _solver_read_host_timing
 Solver.enable_timing = _solver_enable_timing
 Solver.read_timing = _solver_read_timing
