@@ -9,6 +9,8 @@
  *                                                include/cORBmatcher.h:111-117, src/cORBmatcher.cpp:968-1156
  *   the best / second-best Hamming scans of the windowed matchers (SearchByProjection
  *   src/cORBmatcher.cpp:67-163, WindowSearch :326-475) -> mcs_hamming_top2_*.
+ *   both SearchByBoW overloads (src/cORBmatcher.cpp:179-323 relocalisation, :885-966 loop
+ *   detection), one frame against a batch of candidates -> mcs_search_by_bow*.
  *
  * `dim` / `bytes` is the descriptor length in BYTES (the reference passes featDim = 32
  * and loops dim/8 uint64 words).  Device entry points are asynchronous on `stream`.
@@ -192,6 +194,98 @@ int mcs_window_match(int32_t device, int32_t rule, const mcs_window_frame* frame
                      const double* q_xyr, const int32_t* q_cam_lvl, const uint8_t* q_desc,
                      const uint8_t* q_mask, int32_t th, double nnratio, uint8_t* kp_assigned,
                      int32_t* match, int32_t* n_matches);
+
+/* ---- SearchByBoW: relocalisation and loop detection -------------------------------------
+ *   int SearchByBoW(cMultiKeyFrame* pKF, cMultiFrame& F, vpMapPointMatches)
+ *                                          src/cORBmatcher.cpp:179-323  ("overload A"), called per
+ *       candidate keyframe by cTracking::Relocalisation (src/cTracking.cpp:1191-1203)
+ *   int SearchByBoW(cMultiKeyFrame* pKF1, cMultiKeyFrame* pKF2, vpMatches12)
+ *                                          src/cORBmatcher.cpp:885-966  ("overload B"), called per
+ *       loop candidate by cLoopClosing::ComputeSim3 (src/cLoopClosing.cpp:285-304)
+ * Both call sites match ONE frame against a batch of candidates; one call here takes the batch.
+ *
+ * A set is n_frames frames packed back to back: frame k owns keypoints off[k] .. off[k+1] of
+ * desc / mask / angle / has_mp, and its FeatureVector (the CSR form mcs_vocab_transform and
+ * mcs_feature_vector_device emit, feature indices local to the frame) lies at fv_node + off[k],
+ * fv_ptr + off[k] + k (n_kp + 1 entries), fv_feat + off[k], with fv_n[k] node entries.
+ * n_kp_total = off[n_frames] is given on the host (it sizes launches); it must be < 2^19.
+ * For the device entries every pointer is a device pointer, for the host entries a host pointer.
+ *   mask    nullable: mdBRIEF masks (havingMasks, DescriptorDistance64Masked, :2457-2477);
+ *           the two sets of one call have both masks or none
+ *   angle   cv::KeyPoint::angle, read only with check_orientation
+ *   has_mp  nonzero = the keypoint holds a map point that is not bad (:214-220, :903-907,
+ *           :922-927); not read for the frame F of overload A (:185 starts from all-NULL)
+ *   fv_*    not read by overload B (it uses no vocabulary, :901-963) */
+typedef struct mcs_bow_set {
+  int32_t n_frames, n_kp_total;
+  const int32_t* off;        /* [n_frames + 1], off[0] = 0, non-decreasing */
+  const uint8_t* desc;       /* [n_kp_total][bytes] */
+  const uint8_t* mask;       /* nullable [n_kp_total][bytes] */
+  const float* angle;        /* [n_kp_total] */
+  const uint8_t* has_mp;     /* [n_kp_total] */
+  const uint32_t* fv_node;   /* node ids, strictly ascending per frame */
+  const int32_t* fv_ptr;     /* [n_kp_total + n_frames] */
+  const uint32_t* fv_feat;   /* feature (keypoint) indices of each node, in feature order */
+  const int32_t* fv_n;       /* [n_frames] */
+} mcs_bow_set;
+
+/* Workspace of the device entries below: frames of at most max_kp keypoints, batches of at
+ * most max_candidates candidates (overload B keeps candidate slots per query and candidate). */
+typedef struct mcs_bow_workspace mcs_bow_workspace;
+int mcs_bow_workspace_create(int32_t device, int32_t max_kp, int32_t max_candidates,
+                             mcs_bow_workspace** out);
+void mcs_bow_workspace_destroy(mcs_bow_workspace* ws);
+
+/* The FeatureVector of TemplatedVocabulary::transform(features, BowVector&, FeatureVector&,
+ * levelsup) (TemplatedVocabulary.h:1126-1196) from the per-descriptor d_node / d_weight that
+ * mcs_vocab_transform_words_device writes, without leaving the device: d_fv_node ascending
+ * (capacity n), d_fv_ptr (capacity n + 1), d_fv_feat in feature order (capacity n), *d_fv_n.
+ * Descriptors with weight <= 0 (stopped words) are dropped, as mcs_vocab_transform does.
+ * Stream-ordered, no host synchronisation; n <= max_kp. */
+int mcs_feature_vector_device(mcs_bow_workspace* ws, const uint32_t* d_node, const double* d_weight,
+                              int32_t n, uint32_t* d_fv_node, int32_t* d_fv_ptr,
+                              uint32_t* d_fv_feat, int32_t* d_fv_n, void* stream);
+
+/* Overload A for frame f (a set of one frame) against the n_frames keyframes of kfs, one
+ * launch for the batch.  Per keyframe: shared nodes in ascending id (:203-300), KF keypoints
+ * of a node in list order, skipped without a good map point; candidates are the node's F
+ * keypoints not yet assigned in this call; best with strict <, second-best counting
+ * multiplicity (:252-261); accepted when best <= th_low and (double)best < nnratio *
+ * (double)second (:264-266).  check_orientation: the 30-bin histogram of
+ * cvRound((angleKF - angleF [+ 360]) * (1.0f / 30)) and ComputeThreeMaxima (:272-282,
+ * :303-321, :2399-2441); matches outside the kept bins are removed after the walk.
+ * th_low = TH_LOW_ of the cORBmatcher ctor (:46-65): 2 * bytes, or bytes with masks.
+ * Out: d_match_f [n_kf][n_f] = index (local to the keyframe) of the KF keypoint whose map point
+ * F's keypoint received, -1 for none; d_n_matches [n_kf] = the return value per keyframe.
+ * Stream-ordered, no host synchronisation.  MCS_ERR_ARG: bytes not 16 / 32 / 64, one mask
+ * without the other, f->n_frames != 1, sizes above the workspace or >= 2^19.  A FeatureVector
+ * entry that points outside its frame is skipped by the kernel (the host entry rejects it). */
+int mcs_search_by_bow_device(mcs_bow_workspace* ws, const mcs_bow_set* f, const mcs_bow_set* kfs,
+                             int32_t bytes, int32_t th_low, double nnratio,
+                             int32_t check_orientation, int32_t* d_match_f, int32_t* d_n_matches,
+                             void* stream);
+
+/* Host-buffer convenience for one or more candidates: checks the arguments (MCS_ERR_ARG also
+ * for a FeatureVector whose nodes are not strictly ascending or whose ranges are malformed, and
+ * for a feature index >= its frame's keypoint count), then uploads, runs the device entry on
+ * `device` and downloads.  MCS_ERR_NO_DEVICE without a GPU (there is no CPU fallback). */
+int mcs_search_by_bow(int32_t device, const mcs_bow_set* f, const mcs_bow_set* kfs, int32_t bytes,
+                      int32_t th_low, double nnratio, int32_t check_orientation, int32_t* match_f,
+                      int32_t* n_matches);
+
+/* Overload B for keyframe kf1 (a set of one frame) against the n_frames candidates of kf2s:
+ * KF1 keypoints with a good map point in index order, brute force over KF2 keypoints with a
+ * good map point not yet taken (vbMatched2), the same best / second-best rule, accepted when
+ * best < th_low (strict, :952) and the ratio test passes; no orientation check.
+ * Out: d_matches12 [n_kf][n1] = KF2 keypoint index (vpMatches12[idx1] = vpMapPoints2[idx2]) or
+ * -1; d_n_matches [n_kf].  Same error behaviour as overload A. */
+int mcs_search_by_bow_kf_device(mcs_bow_workspace* ws, const mcs_bow_set* kf1,
+                                const mcs_bow_set* kf2s, int32_t bytes, int32_t th_low,
+                                double nnratio, int32_t* d_matches12, int32_t* d_n_matches,
+                                void* stream);
+int mcs_search_by_bow_kf(int32_t device, const mcs_bow_set* kf1, const mcs_bow_set* kf2s,
+                         int32_t bytes, int32_t th_low, double nnratio, int32_t* matches12,
+                         int32_t* n_matches);
 
 #ifdef __cplusplus
 }

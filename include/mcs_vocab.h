@@ -15,6 +15,10 @@
  * Callers: cMultiFrame::ComputeBoW (src/cMultiFrame.cpp:356-363) and
  * cMultiKeyFrame::ComputeBoW (src/cMultiKeyFrame.cpp:105-119), both with levelsup = 4 over the
  * camera-concatenated descriptors (cConverter::toDescriptorVector, src/cConverter.cpp:58-67).
+ * The FeatureVector's consumers are the two cORBmatcher::SearchByBoW overloads
+ * (src/cORBmatcher.cpp:179-323, :885-966): mcs_search_by_bow[_device] takes the fv_node / fv_ptr /
+ * fv_feat arrays below as they are, and mcs_feature_vector_device (mcs_matcher.h) builds them on
+ * the device from mcs_vocab_transform_words_device's d_node / d_weight.
  *
  * Descriptors are FORB's 32 bytes.  Enumerations follow DBoW2 (BowVector.h):
  * weighting TF_IDF = 0, TF = 1, IDF = 2, BINARY = 3; scoring L1_NORM = 0, L2_NORM = 1,

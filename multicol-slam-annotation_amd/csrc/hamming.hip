@@ -5,6 +5,7 @@
 //            SearchForTriangulationRaw          src/cORBmatcher.cpp:968-1156
 //            best/second-best scans             src/cORBmatcher.cpp:67-163, 326-475
 #include "common.hpp"
+#include "ham_dist.hpp"
 #include <map>
 #include <mutex>
 #include "../../include/mcs_matcher.h"
@@ -19,20 +20,6 @@ namespace mcs {
 
 constexpr int kHamThreads = 256;
 constexpr int kHamTile = 256;      // train rows per LDS tile
-
-template <int W>
-__device__ __forceinline__ int ham_dist_v(const uint32_t (&q)[W], const uint4* t4) {
-  int d = 0;
-#pragma unroll
-  for (int w4 = 0; w4 < W / 4; w4++) {
-    const uint4 v = t4[w4];
-    d += __popc(q[4 * w4 + 0] ^ v.x);
-    d += __popc(q[4 * w4 + 1] ^ v.y);
-    d += __popc(q[4 * w4 + 2] ^ v.z);
-    d += __popc(q[4 * w4 + 3] ^ v.w);
-  }
-  return d;
-}
 
 // Top-2 over one (query set, train set) pair; blockIdx.x = query tile, blockIdx.y = pair.
 // Each lane owns kQPT queries (descriptors in VGPRs) so one LDS broadcast read of a train
@@ -369,35 +356,6 @@ __global__ __launch_bounds__(kHamThreads) void k_dense(const uint8_t* __restrict
   for (int j = 0; j < nt_tile; j++) D[(int64_t)qi * nb + t0 + j] = (uint16_t)ham_dist_v<W>(q, &tile[j * (W / 4)]);
 }
 
-// DescriptorDistance64Masked (src/cORBmatcher.cpp:2457-2477): (sum popc(x & m1) +
-// sum popc(x & m2)) / 2 over the whole descriptor, integer division of the total.
-template <int W>
-__device__ __forceinline__ int ham_dist_masked_v(const uint32_t (&q)[W], const uint32_t (&qm)[W],
-                                                 const uint4* t4, const uint4* m4) {
-  int d = 0;
-#pragma unroll
-  for (int w4 = 0; w4 < W / 4; w4++) {
-    const uint4 v = t4[w4], m = m4[w4];
-    const uint32_t x0 = q[4 * w4 + 0] ^ v.x, x1 = q[4 * w4 + 1] ^ v.y;
-    const uint32_t x2 = q[4 * w4 + 2] ^ v.z, x3 = q[4 * w4 + 3] ^ v.w;
-    d += __popc(x0 & qm[4 * w4 + 0]) + __popc(x0 & m.x);
-    d += __popc(x1 & qm[4 * w4 + 1]) + __popc(x1 & m.y);
-    d += __popc(x2 & qm[4 * w4 + 2]) + __popc(x2 & m.z);
-    d += __popc(x3 & qm[4 * w4 + 3]) + __popc(x3 & m.w);
-  }
-  return d >> 1;
-}
-
-template <int W>
-__device__ __forceinline__ void load_desc_row(uint32_t (&q)[W], const uint8_t* row) {
-  const uint4* qp = reinterpret_cast<const uint4*>(row);
-#pragma unroll
-  for (int w4 = 0; w4 < W / 4; w4++) {
-    const uint4 v = qp[w4];
-    q[4 * w4] = v.x; q[4 * w4 + 1] = v.y; q[4 * w4 + 2] = v.z; q[4 * w4 + 3] = v.w;
-  }
-}
-
 static int check_bytes(int bytes) {
   if (bytes != 16 && bytes != 32 && bytes != 64) {
     set_error("descriptor bytes must be 16, 32 or 64");
@@ -516,12 +474,6 @@ __host__ __device__ __forceinline__ bool epi_check(const double* r1, const doubl
                      Etx2[1] * Etx2[1] + Etx2[2] * Etx2[2];
   if (den == 0.0) return false;
   return (nom * nom) / den < thresh;
-}
-
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o, 64));
-  return v;
 }
 
 // ---- SearchForTriangulationRaw on the device (src/cORBmatcher.cpp:1016-1089)

@@ -277,4 +277,95 @@ class PoseOptimizer {
   mcs_ba_ctx* c_ = nullptr;
 };
 
+// cORBmatcher::SearchByBoW, both overloads (src/cORBmatcher.cpp:179-323, :885-966), one frame
+// against a batch of candidates in one call.  A BowFrame is a frame or keyframe as flat arrays.
+struct BowFrame {
+  std::vector<uint8_t> desc;        // [n][bytes] descriptors in keypoint (camera-concatenated) order
+  std::vector<uint8_t> mask;        // empty, or [n][bytes] mdBRIEF masks
+  std::vector<float> angle;         // mvKeys[i].angle (read with checkOrientation only)
+  std::vector<uint8_t> has_mp;      // GetMapPointMatches()[i] && !isBad()
+  std::vector<uint32_t> fv_node;    // mFeatVec: node ids ascending,
+  std::vector<int32_t> fv_ptr;      //   fv_feat[fv_ptr[j] .. fv_ptr[j + 1]) = features of node j
+  std::vector<uint32_t> fv_feat;    //   (mcs_vocab_transform's output)
+};
+
+namespace detail {
+struct BowPacked {
+  std::vector<int32_t> off, fv_ptr, fv_n;
+  std::vector<uint8_t> desc, mask, has_mp;
+  std::vector<float> angle;
+  std::vector<uint32_t> fv_node, fv_feat;
+  mcs_bow_set set{};
+};
+inline void bow_pack(const BowFrame* const* frames, int n_frames, int bytes, bool fv, BowPacked& p) {
+  p.off.assign(1, 0);
+  for (int k = 0; k < n_frames; k++) p.off.push_back(p.off.back() + (int32_t)(frames[k]->desc.size() / bytes));
+  const size_t tot = (size_t)p.off.back();
+  const bool masked = n_frames > 0 && !frames[0]->mask.empty();
+  p.desc.assign(tot * bytes, 0); p.has_mp.assign(tot, 0); p.angle.assign(tot, 0.f);
+  if (masked) p.mask.assign(tot * bytes, 0);
+  p.fv_node.assign(tot, 0); p.fv_feat.assign(tot, 0); p.fv_ptr.assign(tot + n_frames, 0); p.fv_n.assign(n_frames, 0);
+  for (int k = 0; k < n_frames; k++) {
+    const BowFrame& f = *frames[k];
+    const size_t o = (size_t)p.off[k], n = (size_t)(p.off[k + 1] - p.off[k]);
+    if (masked != !f.mask.empty()) throw std::invalid_argument("SearchByBoW: masks for every frame or none");
+    if (n) std::memcpy(&p.desc[o * bytes], f.desc.data(), n * bytes);
+    if (masked && n) std::memcpy(&p.mask[o * bytes], f.mask.data(), n * bytes);
+    for (size_t i = 0; i < n && i < f.has_mp.size(); i++) p.has_mp[o + i] = f.has_mp[i];
+    for (size_t i = 0; i < n && i < f.angle.size(); i++) p.angle[o + i] = f.angle[i];
+    if (!fv) continue;
+    const size_t m = f.fv_node.size();
+    if (m > n || f.fv_feat.size() > n || (m && f.fv_ptr.size() != m + 1))
+      throw std::invalid_argument("SearchByBoW: FeatureVector larger than its frame");
+    p.fv_n[k] = (int32_t)m;
+    for (size_t j = 0; j < m; j++) p.fv_node[o + j] = f.fv_node[j];
+    for (size_t j = 0; j < f.fv_ptr.size(); j++) p.fv_ptr[o + k + j] = f.fv_ptr[j];
+    for (size_t j = 0; j < f.fv_feat.size(); j++) p.fv_feat[o + j] = f.fv_feat[j];
+  }
+  p.set = mcs_bow_set{n_frames, (int32_t)tot, p.off.data(), p.desc.data(), masked ? p.mask.data() : nullptr,
+                      p.angle.data(), p.has_mp.data(), p.fv_node.data(), p.fv_ptr.data(), p.fv_feat.data(),
+                      p.fv_n.data()};
+}
+}  // namespace detail
+
+// SearchByBoW(pKF, F, vpMapPointMatches) for every candidate keyframe of Relocalisation's loop
+// (src/cTracking.cpp:1191-1203).  match_f[k][i] = keypoint of kfs[k] whose map point F's
+// keypoint i received (the caller sets vpMapPointMatches[i] = kfs[k]->GetMapPoint(that)), -1 =
+// NULL.  Returns nmatches per candidate.  th_low = matcher's TH_LOW_ (2 * bytes, or bytes with
+// masks), nnratio / checkOrientation as given to the cORBmatcher ctor.
+inline std::vector<int> SearchByBoW(const BowFrame& F, const std::vector<const BowFrame*>& kfs, int bytes,
+                                    int th_low, double nnratio, bool checkOrientation,
+                                    std::vector<std::vector<int32_t>>& match_f, int device = 0) {
+  detail::BowPacked pf, pk;
+  const BowFrame* fp = &F;
+  detail::bow_pack(&fp, 1, bytes, true, pf);
+  detail::bow_pack(kfs.data(), (int)kfs.size(), bytes, true, pk);
+  const size_t nf = (size_t)pf.set.n_kp_total;
+  std::vector<int32_t> m(kfs.size() * nf + 1), n(kfs.size() + 1);
+  check(mcs_search_by_bow(device, &pf.set, &pk.set, bytes, th_low, nnratio, checkOrientation ? 1 : 0, m.data(),
+                          n.data()), "mcs_search_by_bow");
+  match_f.assign(kfs.size(), std::vector<int32_t>());
+  for (size_t k = 0; k < kfs.size(); k++) match_f[k].assign(m.begin() + k * nf, m.begin() + (k + 1) * nf);
+  return std::vector<int>(n.begin(), n.begin() + kfs.size());
+}
+
+// SearchByBoW(pKF1, pKF2, vpMatches12) for every loop candidate of ComputeSim3
+// (src/cLoopClosing.cpp:285-304).  matches12[k][i1] = keypoint of kf2s[k] (vpMatches12[i1] =
+// its map point), -1 = NULL.
+inline std::vector<int> SearchByBoW(const BowFrame& KF1, const std::vector<const BowFrame*>& kf2s, int bytes,
+                                    int th_low, double nnratio,
+                                    std::vector<std::vector<int32_t>>& matches12, int device = 0) {
+  detail::BowPacked p1, p2;
+  const BowFrame* fp = &KF1;
+  detail::bow_pack(&fp, 1, bytes, false, p1);
+  detail::bow_pack(kf2s.data(), (int)kf2s.size(), bytes, false, p2);
+  const size_t n1 = (size_t)p1.set.n_kp_total;
+  std::vector<int32_t> m(kf2s.size() * n1 + 1), n(kf2s.size() + 1);
+  check(mcs_search_by_bow_kf(device, &p1.set, &p2.set, bytes, th_low, nnratio, m.data(), n.data()),
+        "mcs_search_by_bow_kf");
+  matches12.assign(kf2s.size(), std::vector<int32_t>());
+  for (size_t k = 0; k < kf2s.size(); k++) matches12[k].assign(m.begin() + k * n1, m.begin() + (k + 1) * n1);
+  return std::vector<int>(n.begin(), n.begin() + kf2s.size());
+}
+
 }  // namespace mcs

@@ -154,6 +154,14 @@ SIGNATURES = {
     "mcs_window_search_device": (ctypes.c_int, [_P, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P]),
     "mcs_window_select": (ctypes.c_int, [_I32, _I32, _P, _P, _P, _P, _I32, _I32, ctypes.c_double, _P, _P, _P]),
     "mcs_window_match": (ctypes.c_int, [_I32, _I32, _P, _I32, _P, _P, _P, _P, _I32, ctypes.c_double, _P, _P, _P]),
+    # SearchByBoW (include/mcs_matcher.h; wrappers in mcs_amd/bow_match.py)
+    "mcs_bow_workspace_create": (ctypes.c_int, [_I32, _I32, _I32, _P]),
+    "mcs_bow_workspace_destroy": (None, [_P]),
+    "mcs_feature_vector_device": (ctypes.c_int, [_P, _P, _P, _I32, _P, _P, _P, _P, _P]),
+    "mcs_search_by_bow_device": (ctypes.c_int, [_P, _P, _P, _I32, _I32, ctypes.c_double, _I32, _P, _P, _P]),
+    "mcs_search_by_bow": (ctypes.c_int, [_I32, _P, _P, _I32, _I32, ctypes.c_double, _I32, _P, _P]),
+    "mcs_search_by_bow_kf_device": (ctypes.c_int, [_P, _P, _P, _I32, _I32, ctypes.c_double, _P, _P, _P]),
+    "mcs_search_by_bow_kf": (ctypes.c_int, [_I32, _P, _P, _I32, _I32, ctypes.c_double, _P, _P]),
     # DBoW2 vocabulary (include/mcs_vocab.h)
     "mcs_vocab_create": (_I32, [_I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _P, _I32, _P]),
     "mcs_vocab_destroy": (_I32, [_P]),
