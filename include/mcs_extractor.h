@@ -31,8 +31,9 @@ extern "C" {
  * EDGE_THRESHOLD=25 / PATCH_SIZE=32 of src/mdBRIEFextractorOct.cpp:84-86 apply). */
 typedef struct mcs_extractor_params {
   int32_t nfeatures;       /* 1000 default */
-  float scale_factor;      /* 1.2 default; stored as double((float)x) like the reference */
-  int32_t nlevels;         /* 8 */
+  float scale_factor;      /* 1.2 default; stored as double((float)x) like the reference;
+                              accepted range (1, 2.2f] */
+  int32_t nlevels;         /* 8; accepted range 1..12 */
   int32_t edge_threshold;  /* 25 (unused) */
   int32_t first_level;     /* 0 (unused) */
   int32_t score_type;      /* 0 HARRIS / 1 FAST: only logged by the reference (unused) */
@@ -71,7 +72,14 @@ typedef struct mcs_extractor mcs_extractor;
 void mcs_extractor_default_params(mcs_extractor_params* p);
 
 /* Create an extractor for width x height 8-bit frames; reserves device workspace for up
- * to max_frames camera-frames per batch call.  device = HIP device ordinal. */
+ * to max_frames camera-frames per batch call.  device = HIP device ordinal.
+ * Accepted: 1 < scale_factor <= 2.2f (the float value, 2.2000000477) and 1 <= nlevels <= 12;
+ * scale_factor <= 1 (or NaN) and nlevels outside 1..12 return MCS_ERR_ARG, scale_factor above
+ * 2.2f returns MCS_ERR_UNSUPPORTED (the pyramid kernel's source tile).  Two geometries the
+ * reference itself cannot process return MCS_ERR_UNSUPPORTED: a pyramid level without one
+ * whole 30 px FAST cell in each direction (a level under 74 px wide or high: the reference
+ * divides by zero), and a level whose octree nIni = cvRound((w - 44) / (h - 44)) is 0 (w - 44
+ * at most half of h - 44: the reference indexes out of range). */
 int mcs_extractor_create(const mcs_extractor_params* p, int32_t width, int32_t height,
                          int32_t max_frames, int32_t device, mcs_extractor** out);
 void mcs_extractor_destroy(mcs_extractor* h);

@@ -255,9 +255,6 @@ int mcs_extractor_create(const mcs_extractor_params* p, int32_t width, int32_t h
   h->max_frames = max_frames;
   const Plan& pl = h->plan;
   const size_t F = (size_t)max_frames;
-  if (!(pl.scale_factor <= kMaxScaleFactor)) {
-    delete h; set_error("scale_factor > 2.2 exceeds the pyramid kernel's source tile"); return MCS_ERR_UNSUPPORTED;
-  }
   static bool consts_done[64] = {false};
   if (device < 64 && !consts_done[device]) {
     if ((rc = upload_desc_constants()) != MCS_OK) { delete h; return rc; }

@@ -88,8 +88,14 @@ void zero_runs(const std::vector<CellDesc>& cells, int c, int e, int level, int 
 int build_plan(const mcs_extractor_params& p, int W, int H, Plan& pl) {
   if (W <= 0 || H <= 0 || p.nlevels < 1 || p.nlevels > kMaxLevels || p.nfeatures < 0 ||
       !(p.scale_factor > 1.0f)) {
-    set_error("invalid extractor parameters");
+    set_error("invalid extractor parameters: width, height > 0, nfeatures >= 0, nlevels in 1..12 "
+              "and scale_factor in (1, 2.2] are required");
     return MCS_ERR_ARG;
+  }
+  if (!((double)p.scale_factor <= kMaxScaleFactor)) {
+    set_error("scale_factor > 2.2f exceeds the pyramid kernel's source tile (accepted: 1 < "
+              "scale_factor <= 2.2f)");
+    return MCS_ERR_UNSUPPORTED;
   }
   if (p.desc_size != 16 && p.desc_size != 32 && p.desc_size != 64) {
     set_error("desc_size must be 16, 32 or 64 (src/cTracking.cpp:133)");

@@ -17,7 +17,10 @@ constexpr int kHalfPatch = 16;                 // :85
 constexpr int kMaxCellDim = 64;                // window bound per FAST cell (host-checked)
 constexpr int kMaxCellsPerLevel = 2048;        // LDS prefix table in the octree kernel
 constexpr int kOctMaxL = 1024;                 // octree node-list bound (host-checked)
-constexpr double kMaxScaleFactor = 2.2;        // pyramid source-tile bound (k_pyramid.hip)
+// pyramid source-tile bound (k_pyramid.hip).  The plan holds double((float)scale_factor), so the
+// bound is the float 2.2f widened, not the double 2.2 (which lies below it and would reject a
+// caller who passes the documented maximum).
+constexpr double kMaxScaleFactor = (double)2.2f;
 
 // One FAST cell of ComputeKeyPointsOctTree (:892-948): the detection window is the
 // cell ROI shrunk by 3 px (FAST_t rows/cols [3, n-3)), absolute level coordinates.
