@@ -11,9 +11,22 @@
  *       decl include/cMapPoint.h:90 (GetCameraCenter: src/cMultiKeyFrame.cpp:159-165)
  *
  * Observations are given per point as CSR lists in the order the reference visits its
- * std::map<cMultiKeyFrame*, ...> (the caller's map order; bad keyframes already dropped for
- * ComputeDistinctiveDescriptors, as the reference skips them).  All pointers are device
- * memory; calls are asynchronous on `stream` (hipStream_t, NULL = default).
+ * std::map<cMultiKeyFrame*, std::vector<size_t>> (the caller's map order).  The two calls take
+ * DIFFERENT lists, because the two methods read the map differently:
+ *   - UpdateNormalAndDepth iterates map ENTRIES: d_obs_kf holds every keyframe of the map
+ *     once -- however many of its keypoints (cameras) see the point, even when its index
+ *     vector is empty, and whether or not the keyframe is bad (:470-478 has no isBad test);
+ *   - ComputeDistinctiveDescriptors skips bad keyframes (:322) and takes one descriptor per
+ *     entry of each remaining keyframe's index vector, in vector order (:324-331): d_obs_row
+ *     holds that many rows per keyframe;
+ *   - a bad point returns from both methods before anything is read (:307, :461): give it
+ *     empty lists (or leave it out), its outputs are then left untouched;
+ *   - d_ref_level comes from observations[pRefKF][0] (:484-485): the octave of the FIRST
+ *     index the reference keyframe holds; -1 when the reference keyframe is not in the map
+ *     or its index vector is empty (operator[] default-inserts; the level is then 1).
+ * tests/test_mapside_ref.py::flatten is this rule as code, held to the reference text.
+ * All pointers are device memory; calls are asynchronous on `stream` (hipStream_t,
+ * NULL = default).
  */
 #ifndef MCS_MAPPOINT_H
 #define MCS_MAPPOINT_H
@@ -39,7 +52,7 @@ int mcs_distinctive_descriptors_device(const uint8_t* d_desc, const uint8_t* d_m
                                        uint8_t* d_out_mask, void* stream);
 
 /* UpdateNormalAndDepth for n_points points at positions d_points [n][3]: observing keyframes
- * d_obs_kf[d_obs_ptr[p] .. d_obs_ptr[p+1]) (map order), keyframe centres d_kf_center
+ * d_obs_kf[d_obs_ptr[p] .. d_obs_ptr[p+1]) (map order, each keyframe once), keyframe centres d_kf_center
  * [n_kf][3] (the translation of M_t, GetCameraCenter), reference keyframe d_ref_kf[p] and
  * d_ref_level[p] = octave of the reference keyframe's first observation of the point, or -1
  * when it holds none (the reference then uses level 1); d_scale [n_levels] = mvScaleFactors.

@@ -6,6 +6,10 @@
 //   mcs_distinctive_descriptors_device  <- cMapPoint::ComputeDistinctiveDescriptors
 //                                          (src/cMapPoint.cpp:297-390), after :899-901
 //   mcs_update_normal_depth_device      <- cMapPoint::UpdateNormalAndDepth (:453-496)
+// The two refresh calls take different CSR lists (include/mcs_mappoint.h): `rows` holds one
+// descriptor row per index of every keyframe that is not bad, `okf` every keyframe of the
+// point's observation map once (bad ones and multi-camera ones too); a bad point has empty
+// lists; lvl is the octave of the first index the reference keyframe holds, or -1.
 // Input file (little-endian, written by tests/test_host_cpp.py):
 //   i32 nrig, i32 ncams, f64 mt1[nrig][6], f64 mt2[nrig][6], f64 mc[ncams][6]
 //   i32 nb, i32 nrows, i32 npts_d, u8 desc[nrows][nb], i32 ptr[npts_d+1], i32 rows[ptr[npts_d]]

@@ -839,6 +839,8 @@ class Ctx:
         self.type_names = set()
         self.factories = {}    # env name -> Ty of default elements the code constructs
         self.scalable = {}     # class name -> env helper for `object * scalar`
+        self.binops = {}       # (class name | 'arith', op, class name | 'arith') -> (env helper,
+        #                        result Ty or callable(Ty, Ty) -> Ty): operators of class objects
 
     def add_class(self, spec):
         self.classes[spec.name] = spec
@@ -1126,6 +1128,14 @@ class FuncTranslator:
                 if isinstance(a.ty, Cls) and a.ty.name == "iterator" and b.ty == a.ty:
                     return E("(%s %s %s)" % (a.code, op, b.code), BOOL)
             raise Unsupported("comparison %r %s %r" % (a.ty, op, b.ty))
+        if self.ctx.binops and (isinstance(a.ty, Cls) or isinstance(b.ty, Cls)):
+            key = lambda t: t.name if isinstance(t, Cls) else "arith" if is_arith(t) else None  # noqa: E731
+            hook = self.ctx.binops.get((key(a.ty), op, key(b.ty)))
+            if hook is not None:
+                ca = self.conv(a, DOUBLE) if is_arith(a.ty) else a.code
+                cb = self.conv(b, DOUBLE) if is_arith(b.ty) else b.code
+                rty = hook[1](a.ty, b.ty) if callable(hook[1]) else hook[1]
+                return E("%s(%s, %s)" % (hook[0], ca, cb), rty, obj=is_obj(rty))
         if isinstance(a.ty, Cls) and op == "*" and is_arith(b.ty) and a.ty.name in self.ctx.scalable:
             return E("%s(%s, %s)" % (self.ctx.scalable[a.ty.name], a.code, self.conv(b, DOUBLE)), a.ty)
         if isinstance(a.ty, PtrT) and op in ("+", "-") and is_arith(b.ty):

@@ -180,3 +180,18 @@ def test_gpu_is_in_frustum_matches_oracle(gpu, seed):
     assert np.abs(g_pj.cpu().numpy()[sel] - pj[sel]).max() < 1e-9
     assert np.array_equal(g_lv.cpu().numpy()[sel], lv[sel])
     assert np.abs(g_vc.cpu().numpy()[sel] - vc[sel]).max() < 1e-12
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cams,levels,points", [([0], None, None), ([1], None, None), ([2], None, None),
+                                                (None, 1, None), ([0], None, (1, 2)), (None, None, (0, 85)),
+                                                ([2], None, (0, 257))])
+def test_gpu_is_in_frustum_edge_shapes(gpu, cams, levels, points):
+    """k_in_frustum on the reference-text cases of tests/golden/mapside_ref.npz (boundary
+    pixels, mirror-mask edges, a point on the camera axis, dist exactly on a distance limit,
+    ratio exactly a scale factor) re-run with one camera (C = 1), one scale level (L = 1) and
+    n * C = 1, 255 and 257 threads."""
+    from tests import test_mapside_ref as ms
+    z = ms.fixture()
+    got = ms.gpu_frustum(*ms._frustum_args(z, cams, levels, points))
+    ms.check_frustum(z, got, cams, levels, points)
