@@ -11,6 +11,8 @@
  *   src/cORBmatcher.cpp:67-163, WindowSearch :326-475) -> mcs_hamming_top2_*.
  *   both SearchByBoW overloads (src/cORBmatcher.cpp:179-323 relocalisation, :885-966 loop
  *   detection), one frame against a batch of candidates -> mcs_search_by_bow*.
+ *   the three Fuse overloads (src/cORBmatcher.cpp:1265-1418, :1420-1567, :1570-1719), one set of
+ *   map points against a batch of target keyframes -> mcs_fuse*, mcs_fuse_select.
  *
  * `dim` / `bytes` is the descriptor length in BYTES (the reference passes featDim = 32
  * and loops dim/8 uint64 words).  Device entry points are asynchronous on `stream`.
@@ -286,6 +288,160 @@ int mcs_search_by_bow_kf_device(mcs_bow_workspace* ws, const mcs_bow_set* kf1,
 int mcs_search_by_bow_kf(int32_t device, const mcs_bow_set* kf1, const mcs_bow_set* kf2s,
                          int32_t bytes, int32_t th_low, double nnratio, int32_t* matches12,
                          int32_t* n_matches);
+
+/* ---- Fuse: map-point fusion of local mapping and loop closing ------------------------------
+ *   int Fuse(cMultiKeyFrame* pKF, cMultiKeyFrame* curKF, vector<cMapPoint*>& vpMapPoints, th)
+ *                                          src/cORBmatcher.cpp:1265-1418  (rule 0), called once per
+ *       target keyframe by cLocalMapping::SearchInNeighbors (src/cLocalMapping.cpp:388-457)
+ *   int Fuse(cMultiKeyFrame* pKF, vector<cMapPoint*>& vpMapPoints, th)
+ *                                          src/cORBmatcher.cpp:1420-1567  (rule 1), called once with
+ *       the union of the neighbours' map points (src/cLocalMapping.cpp:453)
+ *   int Fuse(cMultiKeyFrame* pKF, cv::Matx44d Scw, const vector<cMapPoint*>& vpPoints, th)
+ *                                          src/cORBmatcher.cpp:1570-1719  (rule 2), called per
+ *       corrected keyframe by cLoopClosing::SearchAndFuse (src/cLoopClosing.cpp:670-690)
+ * Split: per (target keyframe t, query map point i, camera c) the projection
+ * (WorldToCamHom_fast, src/cam_system_omni.cpp:92-112), isPointInMirrorMask
+ * (src/cam_model_omni.cpp:165-180), the distance test against Get{Min,Max}DistanceInvariance
+ * (src/cMapPoint.cpp:498-508), the predicted level, cMultiKeyFrame::GetFeaturesInArea
+ * (src/cMultiKeyFrame.cpp:703-746) and the best-distance scan do not depend on map state and run
+ * on the device, ONE query set against a batch of T targets per call.  The state-dependent tails
+ * (:1379-1415, :1536-1563, :1692-1715) are mcs_fuse_select on the host, one target at a time.
+ *
+ * What the three rules differ in (all reproduced):
+ *   dist3D is `const float` in rules 0 and 1 (:1306, :1464: cv::norm rounded to float, then
+ *   compared and divided in double) and double in rule 2 (:1623);
+ *   the camera centre is the translation of M_t (cMultiKeyFrame::GetCameraCenter,
+ *   src/cMultiKeyFrame.cpp:159-165; rule 2: Hom2T(Get_M_t()), :1585);
+ *   rule 1 never assigns `dist` (:1511, :1514 discard the result): bestDist is 0 and bestIdx the
+ *   first window candidate whose level passes :1501.  MCS_FUSE_USE_DISTANCE makes rule 1 scan
+ *   distances as rules 0 and 2 do (the evidently intended behaviour; not what the reference runs);
+ *   rule 0 computes E12 = ComputeE(curKF.Get_MtMc_inv(cam) * pKF.Get_MtMc(cam))
+ *   (include/misc.h:235-243, the one-argument form) with `cam` the projection camera in pKF for
+ *   BOTH keyframes (:1392-1396) and tests CheckDistEpipolarLine(ray of curKF keypoint i, ray of
+ *   the best pKF keypoint, E12, 1e-2) (:1390-1398, src/misc.cpp:54-70);
+ *   rule 2 takes M_t = invMat(Rt2Hom(sRcw / s, tcw / s)) (:1576-1585): the caller builds it on
+ *   the host (host/mcs_multicol.hpp does, in the reference's operation order).
+ * Shared: level = min(lower_bound(scaleFactors, dist3D / minDistance), nLevels - 1), radius =
+ * th * scaleFactors[level], a candidate's octave must be level - 1 or level, the first minimum
+ * in GetFeaturesInArea order wins (strict <), a camera contributes when bestDist <= th_low.
+ *
+ * Batch contract: the device result for target t is the reference's result provided no query's
+ * descriptor changed before its turn at t.  Inside a Fuse sequence a map point's descriptor changes only
+ * when it survives a Replace as pMPinKF (ComputeDistinctiveDescriptors, src/cMapPoint.cpp:244);
+ * positions and distances do not change.  mcs_fuse_select reports the REPLACE survivors that are
+ * themselves queries; the caller refreshes those descriptor rows and re-runs the remaining
+ * targets (mcs::Fuse of host/mcs_multicol.hpp does).  Inside ONE target a descriptor can change
+ * before its point's turn only when the point is listed more than once and rule 2 runs it again
+ * (rules 0 and 1 skip the repeat through IsInKeyFrame once it added or was replaced): a point that
+ * added at its first listing, then survived another query's Replace, is scanned at its second
+ * listing with the row computed from its old descriptor.  A caller that lists a point twice under
+ * rule 2 runs that target again when mcs_fuse_select reports the point among the survivors;
+ * mcs::Fuse does not.  q_skip is the caller's snapshot of the
+ * per-target skip condition (isBad / IsInKeyFrame / already found); those only grow during a
+ * sequence, so a snapshot never skips a pair the reference would process. */
+#define MCS_FUSE_USE_DISTANCE 1   /* flags: rule 1 scans descriptor distances */
+
+/* T target keyframes packed back to back: target t owns keypoints off[t] .. off[t+1] of kp_xy /
+ * kp_octave / kp_cam / desc / mask / rays / cell_kp; keypoint and grid indices are local to the
+ * target.  All targets share the rig (m_c, cam, mirror, grid_params) and the scale pyramid.
+ * n_kp_total = off[n_targets] is given on the host.  Every target holds < 2^19 keypoints (the
+ * position field of the selection key): mcs_fuse checks each target and rejects a larger one;
+ * for mcs_fuse_device the per-target counts are device data, so this is the caller's
+ * precondition, and the kernel reads at most the first 2^19 - 1 keypoints of a target.  The
+ * total over the batch is not limited.  The bottom rows of m_t / m_c are 0 0 0 1. */
+typedef struct mcs_fuse_targets {
+  int32_t n_targets, n_kp_total, n_cams, bytes, n_levels, mirror_w, mirror_h;
+  const int32_t* off;          /* [n_targets + 1], off[0] = 0, non-decreasing */
+  const float* kp_xy;          /* [n_kp_total][2] mvKeys pt */
+  const int32_t* kp_octave;    /* [n_kp_total] */
+  const int32_t* kp_cam;       /* [n_kp_total] keypoint_to_cam; read by mcs_fuse only (grid build) */
+  const uint8_t* desc;         /* [n_kp_total][bytes] */
+  const uint8_t* mask;         /* nullable [n_kp_total][bytes] mdBRIEF masks (havingMasks) */
+  const double* rays;          /* [n_kp_total][3] GetKeyPointRay; rule 0 only */
+  const double* m_t;           /* [n_targets][16] Get_M_t(), row-major 4x4 */
+  const double* m_c;           /* [n_cams][16] M_c, row-major 4x4 */
+  const double* cam;           /* [n_cams][17] as mcs_is_in_frustum_device: c d e u0 v0 invP[12] */
+  const uint8_t* mirror;       /* [n_cams][mirror_h][mirror_w] mirrorMasks[0] */
+  const double* grid_params;   /* [n_cams][4] as mcs_frame_grid_build */
+  const double* scale;         /* [n_levels] mvScaleFactors */
+  const int32_t* cell_ptr;     /* [n_targets][n_cams*64*48 + 1] mcs_frame_grid_build per target */
+  const int32_t* cell_kp;      /* [n_kp_total], target t's list at off[t]; mcs_fuse builds both */
+} mcs_fuse_targets;
+
+typedef struct mcs_fuse_queries {
+  int32_t nq;
+  const double* pos;           /* [nq][3] GetWorldPos */
+  const double* dist;          /* [nq][2] mfMinDistance, mfMaxDistance (the 0.8 / 1.2 are applied) */
+  const uint8_t* desc;         /* [nq][bytes] GetDescriptorPtr */
+  const uint8_t* mask;         /* nullable [nq][bytes]; given iff the targets have masks */
+  const double* rays;          /* rule 0: [nq][3] curKF->GetKeyPointRay(i) */
+  const double* m_t;           /* rule 0: [16] curKF Get_M_t() */
+} mcs_fuse_queries;
+
+/* Device scratch of mcs_fuse_device (per target and camera: M_t M_c and, for rule 0, E12). */
+typedef struct mcs_fuse_workspace mcs_fuse_workspace;
+int mcs_fuse_workspace_create(int32_t device, int32_t max_targets, mcs_fuse_workspace** out);
+void mcs_fuse_workspace_destroy(mcs_fuse_workspace* ws);
+
+/* The device part for all targets in two launches.  Every pointer inside targets / queries and
+ * every d_* is a device pointer.  Out, each [n_targets][nq][n_cams]:
+ *   d_best_kp    bestIdx (local to the target) when bestDist <= th_low, else -1
+ *   d_best_dist  bestDist of the scan (also when above th_low); INT_MAX when the camera was left
+ *                before the scan or no candidate passed the level test
+ *   d_epi_ok     rule 0 (else nullable, not written): the CheckDistEpipolarLine verdict for every
+ *                hit, 0 where best_kp is -1; whether the text consults it depends on map state
+ * d_q_skip nullable [n_targets][nq]: nonzero = -1 / INT_MAX / 0 for all cameras, no work.
+ * th = the search radius factor (2.5 / 3.0 in the callers), th_low = TH_LOW_ of the cORBmatcher
+ * ctor (:46-65).  Stream-ordered, no host synchronisation, no allocation with a workspace; ws
+ * NULL = a temporary one is allocated and freed (which synchronises).  Offsets, counts and grid
+ * entries are device data and are clamped in the kernel: a malformed set reads nothing outside
+ * its buffers.  MCS_ERR_ARG: rule outside 0..2, bytes not 16 / 32 / 64, more than 8 cameras,
+ * a mask on one side only, n_targets above the workspace, a null buffer; mcs_fuse also for a
+ * target of 2^19 keypoints or more and for malformed offsets. */
+int mcs_fuse_device(mcs_fuse_workspace* ws, int32_t rule, int32_t flags,
+                    const mcs_fuse_targets* targets, const mcs_fuse_queries* queries, double th,
+                    int32_t th_low, const uint8_t* d_q_skip, int32_t* d_best_kp,
+                    int32_t* d_best_dist, uint8_t* d_epi_ok, void* stream);
+
+/* Host-buffer form for the reference's call sites: builds every target's grid
+ * (mcs_frame_grid_build; cell_ptr / cell_kp of `targets` are ignored), uploads, runs
+ * mcs_fuse_device on `device` and downloads.  MCS_ERR_NO_DEVICE without a GPU. */
+int mcs_fuse(int32_t device, int32_t rule, int32_t flags, const mcs_fuse_targets* targets,
+             const mcs_fuse_queries* queries, double th, int32_t th_low, const uint8_t* q_skip,
+             int32_t* best_kp, int32_t* best_dist, uint8_t* epi_ok);
+
+/* The state-dependent tail of Fuse for ONE target (:1279-1287 + :1379-1415, :1433-1440 +
+ * :1536-1563, :1596-1602 + :1692-1715) over a flat stand-in of the map.  Host code, no GPU.
+ *   q_mp [nq]             map-point id of query i, -1 = NULL (skipped)
+ *   best_kp [nq][n_cams]  the target's rows of mcs_fuse_device; epi_ok likewise (rule 0)
+ *   mp_bad [n_mp]         in/out cMapPoint::isBad
+ *   mp_in_kf [n_mp]       in/out cMapPoint::IsInKeyFrame(target) (src/cMapPoint.cpp:447-451)
+ *   kp_mp [n_kp]          in/out the target's mvpMapPoints as ids, -1 = NULL.  A map point with
+ *                         mp_in_kf set observes the target at exactly the slots that hold it.
+ * Queries in order; a query is skipped when bad or in the keyframe (rules 0, 1) or when bad or in
+ * spAlreadyFound = the non-bad points in the slots at entry (rule 2, :1588, :1601).  For each
+ * camera with best_kp >= 0, in camera order: an occupied slot fuses when its point is not bad
+ * (rule 0: and epi_ok), REPLACE = pMP->Replace(pMPinKF) (src/cMapPoint.cpp:208-250) then
+ * ++nFused (also when Replace returns early on equal ids); an empty slot gives ADD =
+ * AddObservation (:90-96) + AddMapPoint (src/cMultiKeyFrame.cpp:273-277).  The effects on the
+ * target's own state are applied as the text does: ADD fills the slot and sets mp_in_kf; REPLACE
+ * marks the query bad, clears its mp_in_kf and moves the slots it holds to the survivor, or
+ * erases them when the survivor is already in the keyframe (the IsInKeyFrame branch of Replace);
+ * a query that has turned bad still runs its remaining cameras.
+ * Out: actions [n_actions][4] = (kind, query, keypoint, other_id) in execution order, kind
+ * MCS_FUSE_ADD (other_id = the query's map point) or MCS_FUSE_REPLACE (other_id = the
+ * survivor); the caller replays them onto the other keyframes of its map.  action_cap >=
+ * nq * n_cams always suffices (MCS_ERR_CAPACITY otherwise).  *n_fused = the return value.
+ * requery_ids (nullable, capacity nq) / *n_requery: the distinct REPLACE survivors (other than
+ * the replaced point itself) that are also in q_mp, in order of first survival: their
+ * descriptors change (batch contract above). */
+#define MCS_FUSE_ADD 0
+#define MCS_FUSE_REPLACE 1
+int mcs_fuse_select(int32_t rule, int32_t nq, int32_t n_cams, const int32_t* q_mp,
+                    const int32_t* best_kp, const uint8_t* epi_ok, int32_t n_mp, uint8_t* mp_bad,
+                    uint8_t* mp_in_kf, int32_t n_kp, int32_t* kp_mp, int32_t* actions,
+                    int32_t action_cap, int32_t* n_actions, int32_t* n_fused,
+                    int32_t* requery_ids, int32_t* n_requery);
 
 #ifdef __cplusplus
 }

@@ -8,97 +8,11 @@
 // cayley2rot include/misc.h:134-162, cConverter::invMat src/cConverter.cpp:31-44.
 // Compiled with -ffp-contract=off; double ops spelled with _rn intrinsics where an FMA could
 // otherwise be formed, so every rounding follows the reference's expression order.
-#include "common.hpp"
+#include "proj_window.hpp"
 #include "../../include/mcs_frame.h"
 
 namespace mcs {
 namespace frm {
-
-constexpr int kGridCols = 64, kGridRows = 48;   // FRAME_GRID_COLS / ROWS (include/cMultiFrame.h:47-48)
-
-__device__ __forceinline__ double horner_n(const double* c, int s, double x) {   // misc.h:117-124
-  double r = 0.0;
-  for (int i = s - 1; i >= 0; i--) r = __dadd_rn(__dmul_rn(r, x), c[i]);
-  return r;
-}
-
-// ImgToWorld (cam_model_omni.cpp:49-67)
-__device__ void img_to_world(const mcs_cam_model& m, double u, double v, double* X) {
-  const double invAffine = __dsub_rn(m.c, __dmul_rn(m.d, m.e));
-  const double u_t = __dsub_rn(u, m.u0), v_t = __dsub_rn(v, m.v0);
-  double x = __ddiv_rn(__dsub_rn(u_t, __dmul_rn(m.d, v_t)), invAffine);
-  double y = __ddiv_rn(__dadd_rn(__dmul_rn(-m.e, u_t), __dmul_rn(m.c, v_t)), invAffine);
-  const double X2 = __dmul_rn(x, x), Y2 = __dmul_rn(y, y);
-  double z = -horner_n(m.p, m.p_deg, __dsqrt_rn(__dadd_rn(X2, Y2)));
-  const double norm = __dsqrt_rn(__dadd_rn(__dadd_rn(X2, Y2), __dmul_rn(z, z)));
-  X[0] = __ddiv_rn(x, norm); X[1] = __ddiv_rn(y, norm); X[2] = __ddiv_rn(z, norm);
-}
-
-// cayley2rot (misc.h:134-162): R = (1 / scale) * R
-__device__ void cay2rot(const double* c, double* R) {
-  const double c1 = c[0], c2 = c[1], c3 = c[2];
-  const double c1s = __dmul_rn(c1, c1), c2s = __dmul_rn(c2, c2), c3s = __dmul_rn(c3, c3);
-  const double scale = __dadd_rn(__dadd_rn(__dadd_rn(1.0, c1s), c2s), c3s);
-  const double inv = __ddiv_rn(1.0, scale);
-  R[0] = __dmul_rn(inv, __dsub_rn(__dsub_rn(__dadd_rn(1.0, c1s), c2s), c3s));
-  R[1] = __dmul_rn(inv, __dmul_rn(2.0, __dsub_rn(__dmul_rn(c1, c2), c3)));
-  R[2] = __dmul_rn(inv, __dmul_rn(2.0, __dadd_rn(__dmul_rn(c1, c3), c2)));
-  R[3] = __dmul_rn(inv, __dmul_rn(2.0, __dadd_rn(__dmul_rn(c1, c2), c3)));
-  R[4] = __dmul_rn(inv, __dsub_rn(__dadd_rn(__dsub_rn(1.0, c1s), c2s), c3s));
-  R[5] = __dmul_rn(inv, __dmul_rn(2.0, __dsub_rn(__dmul_rn(c2, c3), c1)));
-  R[6] = __dmul_rn(inv, __dmul_rn(2.0, __dsub_rn(__dmul_rn(c1, c3), c2)));
-  R[7] = __dmul_rn(inv, __dmul_rn(2.0, __dadd_rn(__dmul_rn(c2, c3), c1)));
-  R[8] = __dmul_rn(inv, __dadd_rn(__dsub_rn(__dsub_rn(1.0, c1s), c2s), c3s));
-}
-
-// M = M_t * M_c as 4x4 products (Matx sum over k = 0..3 left to right): R [9], t [3]
-__device__ void mtmc(const double* pose, const double* mc, double* R, double* t) {
-  double Rt[9], Rc[9];
-  cay2rot(pose, Rt);
-  cay2rot(mc, Rc);
-  for (int i = 0; i < 3; i++) {
-    for (int j = 0; j < 3; j++) {
-      double s = __dmul_rn(Rt[3 * i], Rc[j]);
-      s = __dadd_rn(s, __dmul_rn(Rt[3 * i + 1], Rc[3 + j]));
-      s = __dadd_rn(s, __dmul_rn(Rt[3 * i + 2], Rc[6 + j]));
-      s = __dadd_rn(s, __dmul_rn(pose[3 + i], 0.0));
-      R[3 * i + j] = s;
-    }
-    double s = __dmul_rn(Rt[3 * i], mc[3]);
-    s = __dadd_rn(s, __dmul_rn(Rt[3 * i + 1], mc[4]));
-    s = __dadd_rn(s, __dmul_rn(Rt[3 * i + 2], mc[5]));
-    s = __dadd_rn(s, __dmul_rn(pose[3 + i], 1.0));
-    t[i] = s;
-  }
-}
-
-// WorldToCamHom_fast (cam_system_omni.cpp:92-112): invMat(M_t M_c) * [X 1], then WorldToImg
-__device__ void world_to_cam_img(const double* R, const double* t, const double* cam,
-                                 const double* X, double& u, double& v) {
-  double ti[3];   // invMat: R' = R^T, t' = -R' t (cConverter.cpp:31-44)
-  for (int i = 0; i < 3; i++) {
-    double s = __dmul_rn(-R[i], t[0]);
-    s = __dadd_rn(s, __dmul_rn(-R[3 + i], t[1]));
-    s = __dadd_rn(s, __dmul_rn(-R[6 + i], t[2]));
-    ti[i] = s;
-  }
-  double Xc[3];
-  for (int i = 0; i < 3; i++) {
-    double s = __dmul_rn(R[i], X[0]);
-    s = __dadd_rn(s, __dmul_rn(R[3 + i], X[1]));
-    s = __dadd_rn(s, __dmul_rn(R[6 + i], X[2]));
-    s = __dadd_rn(s, __dmul_rn(ti[i], 1.0));
-    Xc[i] = s;
-  }
-  const double x = Xc[0], y = Xc[1], z = Xc[2];   // WorldToImg (cam_model_omni.cpp:147-163)
-  double norm = __dsqrt_rn(__dadd_rn(__dmul_rn(x, x), __dmul_rn(y, y)));
-  if (norm == 0.0) norm = 1e-14;
-  const double theta = atan(__ddiv_rn(-z, norm));
-  const double rho = horner_n(cam + 5, 12, theta);
-  const double uu = __dmul_rn(__ddiv_rn(x, norm), rho), vv = __dmul_rn(__ddiv_rn(y, norm), rho);
-  u = __dadd_rn(__dadd_rn(__dmul_rn(uu, cam[0]), __dmul_rn(vv, cam[1])), cam[3]);
-  v = __dadd_rn(__dadd_rn(__dmul_rn(uu, cam[2]), vv), cam[4]);
-}
 
 __global__ __launch_bounds__(256) void k_keypoint_rays(const mcs_keypoint* __restrict__ kps,
                                                        const int32_t* __restrict__ counts, int F,

@@ -1,0 +1,418 @@
+// cORBmatcher::Fuse on the device: the part of the three overloads that does not depend on map
+// state, for ONE query set of map points against a batch of T target keyframes per call.
+//
+// Reference (billamiable/MultiCol-SLAM-Annotation):
+//   Fuse(pKF, curKF, vpMapPoints, th)   (rule 0)         src/cORBmatcher.cpp:1265-1418
+//   Fuse(pKF, vpMapPoints, th)          (rule 1)         src/cORBmatcher.cpp:1420-1567
+//   Fuse(pKF, Scw, vpPoints, th)        (rule 2)         src/cORBmatcher.cpp:1570-1719
+//   cMultiKeyFrame::GetFeaturesInArea                    src/cMultiKeyFrame.cpp:703-746
+//   cMultiKeyFrame::GetCameraCenter                      src/cMultiKeyFrame.cpp:159-165
+//   WorldToCamHom_fast / isPointInMirrorMask             src/cam_system_omni.cpp:92-112,
+//                                                        src/cam_model_omni.cpp:165-180
+//   Get{Min,Max}DistanceInvariance                       src/cMapPoint.cpp:498-508
+//   ComputeE(Trel), CheckDistEpipolarLine                include/misc.h:235-243, src/misc.cpp:54-70
+// Per (target t, query i, camera c): project, mirror mask, distance window, predicted level,
+// GetFeaturesInArea, best Hamming distance.  The state-dependent tails (:1379-1415, :1536-1563,
+// :1692-1715) are mcs_fuse_select (fuse_select.cpp) on the host.
+// Compiled with -ffp-contract=off; every rounding follows the reference's expression order.
+#include "proj_window.hpp"
+#include <algorithm>
+#include <climits>
+#include <vector>
+
+namespace mcs {
+namespace fuse {
+
+constexpr int kWPB = 4;            // waves per 256-thread workgroup, one (t, i, c) each
+constexpr int kPosBits = 20;       // key = dist << 20 | position in the window's enumeration
+constexpr int kMaxCams = 8;
+constexpr int kMaxKpPerTarget = 1 << 19;
+constexpr double kEpiThresh = 1e-2;   // :1398
+
+struct Args {
+  int T, nq, C, bytes, L, mw, mh, n_kp_total, rule, use_dist, th_low;
+  double th;
+  const int32_t* off; const float* kp_xy; const int32_t* kp_oct; const uint8_t* desc;
+  const uint8_t* mask; const double* rays; const double* m_t; const double* cam;
+  const uint8_t* mirror; const double* gp; const double* scale;
+  const int32_t* cell_ptr; const int32_t* cell_kp;
+  const double* q_pos; const double* q_dist; const uint8_t* q_desc; const uint8_t* q_mask;
+  const double* q_rays;
+  const double* Rt; const double* E;   // workspace: [T][C][12] (R, t of M_t M_c), [T][C][9]
+  const uint8_t* q_skip;
+  int32_t* best_kp; int32_t* best_dist; uint8_t* epi_ok;
+};
+
+// One thread per (t, c): rows 0..2 of M_t M_c, and for rule 0
+// E12 = ComputeE(curKF.Get_MtMc_inv(c) * pKF.Get_MtMc(c)) (:1394-1396, misc.h:235-243).
+// Every product is cv::Matx's s = 0; s += a(i,k) b(k,j); the matrices' bottom rows are 0 0 0 1.
+__global__ __launch_bounds__(64) void k_fuse_setup(const double* __restrict__ m_t,
+                                                   const double* __restrict__ m_c,
+                                                   const double* __restrict__ cur_mt, int T, int C,
+                                                   int rule, double* __restrict__ Rt,
+                                                   double* __restrict__ E) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= T * C) return;
+  const int t = idx / C, c = idx - t * C;
+  double R[9], tt[3];
+  frm::mtmc44(m_t + 16 * (int64_t)t, m_c + 16 * c, R, tt);
+  double* o = Rt + 12 * (int64_t)idx;
+  for (int k = 0; k < 9; k++) o[k] = R[k];
+  for (int k = 0; k < 3; k++) o[9 + k] = tt[k];
+  if (rule != 0) return;
+  double R1[9], t1[3], Ri[9], ti[3];
+  frm::mtmc44(cur_mt, m_c + 16 * c, R1, t1);
+  for (int i = 0; i < 3; i++)   // invMat (cConverter.cpp:31-44): R' = R^T, t' = -R' t
+    for (int j = 0; j < 3; j++) Ri[3 * i + j] = R1[3 * j + i];
+  for (int i = 0; i < 3; i++) {
+    double s = 0.0;
+    for (int k = 0; k < 3; k++) s = __dadd_rn(s, __dmul_rn(-Ri[3 * i + k], t1[k]));
+    ti[i] = s;
+  }
+  double Rr[9], tr[3];   // Trel = T1 * T2, rows 0..2
+  for (int i = 0; i < 3; i++) {
+    for (int j = 0; j < 3; j++) {
+      double s = 0.0;
+      for (int k = 0; k < 3; k++) s = __dadd_rn(s, __dmul_rn(Ri[3 * i + k], R[3 * k + j]));
+      Rr[3 * i + j] = __dadd_rn(s, __dmul_rn(ti[i], 0.0));
+    }
+    double s = 0.0;
+    for (int k = 0; k < 3; k++) s = __dadd_rn(s, __dmul_rn(Ri[3 * i + k], tt[k]));
+    tr[i] = __dadd_rn(s, __dmul_rn(ti[i], 1.0));
+  }
+  double ss = 0.0;   // t /= cv::norm(t): times 1. / sqrt(in-order sum of squares)
+  for (int k = 0; k < 3; k++) ss = __dadd_rn(ss, __dmul_rn(tr[k], tr[k]));
+  const double ia = __ddiv_rn(1.0, __dsqrt_rn(ss));
+  for (int k = 0; k < 3; k++) tr[k] = __dmul_rn(tr[k], ia);
+  const double S[9] = {0.0, -tr[2], tr[1], tr[2], 0.0, -tr[0], -tr[1], tr[0], 0.0};   // Skew
+  double* e = E + 9 * (int64_t)idx;
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) {
+      double s = 0.0;
+      for (int k = 0; k < 3; k++) s = __dadd_rn(s, __dmul_rn(S[3 * i + k], Rr[3 * k + j]));
+      e[3 * i + j] = s;
+    }
+}
+
+// The front half of one (t, i, c) (:1295-1327 and its twins): false = the camera is left before
+// the window; else the projection, the predicted level and the radius.  Wave-uniform.
+__device__ __forceinline__ bool project(const Args& a, int t, int i, int c, double* u, double* v,
+                                        int* level, double* radius) {
+  const double* Rt = a.Rt + 12 * ((int64_t)t * a.C + c);
+  const double* P = a.q_pos + 3 * (int64_t)i;
+  frm::world_to_cam_img(Rt, Rt + 9, a.cam + 17 * c, P, *u, *v);
+  // isPointInMirrorMask(u, v, 0): cvRound, bounds (> 0 and < size), mask > 0
+  const int ur = (int)rint(*u), vr = (int)rint(*v);
+  if (ur >= a.mw || ur <= 0 || vr >= a.mh || vr <= 0) return false;
+  if (a.mirror[(int64_t)c * a.mw * a.mh + (int64_t)vr * a.mw + ur] == 0) return false;
+  const double maxD = __dmul_rn(1.2, a.q_dist[2 * (int64_t)i + 1]);
+  const double minD = __dmul_rn(0.8, a.q_dist[2 * (int64_t)i]);
+  const double* Mt = a.m_t + 16 * (int64_t)t;   // Ow = Hom2T(M_t)
+  const double PO[3] = {__dsub_rn(P[0], Mt[3]), __dsub_rn(P[1], Mt[7]), __dsub_rn(P[2], Mt[11])};
+  double d = __dsqrt_rn(__dadd_rn(__dadd_rn(__dmul_rn(PO[0], PO[0]), __dmul_rn(PO[1], PO[1])),
+                                  __dmul_rn(PO[2], PO[2])));
+  if (a.rule != 2) d = (double)(float)d;   // `const float dist3D` (:1306, :1464); double at :1623
+  if (d < minD || d > maxD) return false;
+  const double ratio = __ddiv_rn(d, minD);
+  int lv = 0;
+  while (lv < a.L && a.scale[lv] < ratio) lv++;
+  if (lv >= a.L) lv = a.L - 1;
+  *level = lv;
+  *radius = __dmul_rn(a.th, a.scale[lv]);
+  return true;
+}
+
+// One wave per (t, i, c).  Every lane computes the front half (it is wave-uniform); the window is
+// walked as k_window does: cells 64 at a time in ix-major order, a wave prefix sum over the cell
+// sizes flattens their keypoints.  A candidate passing |dx| <= r && |dy| <= r and the level test
+// gets the key dist << 20 | position-in-enumeration; the wave minimum is the reference's first
+// minimum under strict <.  Offsets, cell ranges and cell entries are clamped to the target.
+__global__ __launch_bounds__(256) void k_fuse(Args a) {
+  const int lane = threadIdx.x & 63;
+  const int64_t w = (int64_t)blockIdx.x * kWPB + (threadIdx.x >> 6);
+  if (w >= (int64_t)a.T * a.nq * a.C) return;
+  const int c = (int)(w % a.C);
+  const int64_t ti = w / a.C;
+  const int i = (int)(ti % a.nq), t = (int)(ti / a.nq);
+  int bk = -1, bd = INT_MAX;
+  uint8_t ep = 0;
+  double u, v, r;
+  int lv, x0, x1, y0, y1;
+  const bool skip = a.q_skip && a.q_skip[ti] != 0;
+  if (!skip && project(a, t, i, c, &u, &v, &lv, &r) &&
+      win::cell_range(a.gp + 4 * c, u, v, r, &x0, &x1, &y0, &y1)) {
+    const int o = min(max(a.off[t], 0), a.n_kp_total);
+    // a target holds < 2^19 keypoints (position field of the key); the host entry rejects more
+    const int n_t = min(min(max(a.off[t + 1] - o, 0), a.n_kp_total - o), kMaxKpPerTarget - 1);
+    const int32_t* cptr = a.cell_ptr + (int64_t)t * (a.C * win::kCols * win::kRows + 1);
+    const int32_t* ckp = a.cell_kp + o;
+    const uint8_t* qd = a.q_desc + (int64_t)i * a.bytes;
+    const uint8_t* qm = a.q_mask ? a.q_mask + (int64_t)i * a.bytes : nullptr;
+    uint32_t best = 0xFFFFFFFFu;
+    int bestk = -1, pos = 0;
+    const int ncy = y1 - y0 + 1, ncell = (x1 - x0 + 1) * ncy;
+    for (int cb = 0; cb < ncell; cb += 64) {
+      const int ci = cb + lane;
+      int start = 0, len = 0;
+      if (ci < ncell) {
+        const int cell = (c * win::kCols + x0 + ci / ncy) * win::kRows + y0 + ci % ncy;
+        start = min(max(cptr[cell], 0), n_t);
+        len = min(max(cptr[cell + 1] - start, 0), n_t - start);
+      }
+      const int incl = dev::wave_incl_scan(len);
+      const int off = incl - len;
+      const int tot = __shfl(incl, 63);
+      for (int e0 = 0; e0 < tot; e0 += 64) {
+        const int e = e0 + lane;
+        int ow = 0;   // owning cell = the last lane whose offset is <= e
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1)
+          if (__shfl(off, ow + s) <= e) ow += s;
+        const int so = __shfl(start, ow), oo = __shfl(off, ow);
+        if (e < tot) {
+          const int k = ckp[so + (e - oo)];
+          if (k >= 0 && k < n_t) {
+            const int64_t g = (int64_t)o + k;
+            const int oc = a.kp_oct[g];
+            const double dx = (double)a.kp_xy[2 * g] - u, dy = (double)a.kp_xy[2 * g + 1] - v;
+            if (fabs(dx) <= r && fabs(dy) <= r && !(oc < lv - 1 || oc > lv)) {
+              const int dist = a.use_dist ? win::ham(qd, a.desc + g * a.bytes, qm,
+                                                     a.mask ? a.mask + g * a.bytes : nullptr, a.bytes)
+                                          : 0;   // rule 1 as written never assigns dist (:1507-1514)
+              const uint32_t key = ((uint32_t)dist << kPosBits) | ((uint32_t)(pos + e) & ((1u << kPosBits) - 1));
+              if (key < best) { best = key; bestk = k; }
+            }
+          }
+        }
+      }
+      pos += tot;
+    }
+    uint32_t mn = best;
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) mn = min(mn, (uint32_t)__shfl_xor((int)mn, s, 64));
+    if (mn != 0xFFFFFFFFu) {
+      const int src = __ffsll((unsigned long long)__ballot(best == mn)) - 1;
+      const int k = __shfl(bestk, src);
+      bd = (int)(mn >> kPosBits);
+      if (bd <= a.th_low) {
+        bk = k;
+        if (a.rule == 0 && a.epi_ok)
+          ep = epi_check(a.q_rays + 3 * (int64_t)i, a.rays + 3 * ((int64_t)o + k),
+                         a.E + 9 * ((int64_t)t * a.C + c), kEpiThresh) ? 1 : 0;
+      }
+    }
+  }
+  if (lane == 0) {
+    a.best_kp[w] = bk;
+    a.best_dist[w] = bd;
+    if (a.epi_ok) a.epi_ok[w] = ep;
+  }
+}
+
+// device allocations of one host-buffer call, released on every return path
+struct DevBufs {
+  std::vector<void*> p;
+  hipError_t err = hipSuccess;
+  template <class T> T* alloc(size_t n) {
+    void* q = nullptr;
+    if (err == hipSuccess) err = hipMalloc(&q, std::max<size_t>(1, n) * sizeof(T));
+    if (q) p.push_back(q);
+    return static_cast<T*>(q);
+  }
+  template <class T> T* up(const T* h, size_t n) {
+    T* d = alloc<T>(n);
+    if (err == hipSuccess && h && n) err = hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice);
+    return d;
+  }
+  ~DevBufs() { for (void* q : p) (void)hipFree(q); }
+};
+
+static int check_args(int rule, const mcs_fuse_targets* tg, const mcs_fuse_queries* q) {
+  if (!tg || !q) { set_error("fuse: null targets / queries"); return MCS_ERR_ARG; }
+  if (rule < 0 || rule > 2) { set_error("fuse: rule must be 0, 1 or 2"); return MCS_ERR_ARG; }
+  if (tg->bytes != 16 && tg->bytes != 32 && tg->bytes != 64) { set_error("fuse: bytes must be 16, 32 or 64"); return MCS_ERR_ARG; }
+  if (tg->n_cams < 1 || tg->n_cams > kMaxCams) { set_error("fuse: 1 to 8 cameras"); return MCS_ERR_ARG; }
+  if (tg->n_targets < 0 || tg->n_kp_total < 0 || q->nq < 0 || tg->n_levels < 1 || tg->mirror_w < 1 || tg->mirror_h < 1) {
+    set_error("fuse: negative count or empty pyramid / mirror mask");
+    return MCS_ERR_ARG;
+  }
+  if ((tg->mask != nullptr) != (q->mask != nullptr)) { set_error("fuse: descriptor masks for the queries and the targets, or for neither"); return MCS_ERR_ARG; }
+  if ((int64_t)tg->n_targets * q->nq * tg->n_cams >= (int64_t)INT_MAX * kWPB) { set_error("fuse: batch too large for one launch"); return MCS_ERR_ARG; }
+  if (tg->n_targets > 0 && q->nq > 0) {
+    if (!tg->off || !tg->m_t || !tg->m_c || !tg->cam || !tg->mirror || !tg->grid_params || !tg->scale ||
+        !q->pos || !q->dist || !q->desc || (rule == 0 && (!q->rays || !q->m_t)) ||
+        (tg->n_kp_total > 0 && (!tg->kp_xy || !tg->kp_octave || !tg->desc || (rule == 0 && !tg->rays)))) {
+      set_error("fuse: null buffer");
+      return MCS_ERR_ARG;
+    }
+  }
+  return MCS_OK;
+}
+
+}  // namespace fuse
+}  // namespace mcs
+
+using namespace mcs;
+
+struct mcs_fuse_workspace {
+  int device = 0, max_targets = 0;
+  double* Rt = nullptr;
+  double* E = nullptr;
+};
+
+extern "C" {
+
+int mcs_fuse_workspace_create(int32_t device, int32_t max_targets, mcs_fuse_workspace** out) {
+  if (!out || max_targets < 1) { set_error("fuse workspace: bad argument"); return MCS_ERR_ARG; }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+    set_error("no HIP device visible (no CPU fallback)");
+    return MCS_ERR_NO_DEVICE;
+  }
+  if (device < 0 || device >= ndev) { set_error("fuse workspace: no such device"); return MCS_ERR_ARG; }
+  MCS_HIP_CHECK(hipSetDevice(device));
+  mcs_fuse_workspace* w = new mcs_fuse_workspace;
+  w->device = device;
+  w->max_targets = max_targets;
+  const size_t n = (size_t)max_targets * fuse::kMaxCams;
+  hipError_t e = hipMalloc((void**)&w->Rt, n * 12 * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void**)&w->E, n * 9 * sizeof(double));
+  if (e != hipSuccess) {
+    mcs_fuse_workspace_destroy(w);
+    set_hip_error(e, "fuse workspace", __FILE__, __LINE__);
+    return MCS_ERR_HIP;
+  }
+  *out = w;
+  return MCS_OK;
+}
+
+void mcs_fuse_workspace_destroy(mcs_fuse_workspace* w) {
+  if (!w) return;
+  (void)hipSetDevice(w->device);
+  if (w->Rt) (void)hipFree(w->Rt);
+  if (w->E) (void)hipFree(w->E);
+  delete w;
+}
+
+int mcs_fuse_device(mcs_fuse_workspace* ws, int32_t rule, int32_t flags,
+                    const mcs_fuse_targets* tg, const mcs_fuse_queries* q, double th,
+                    int32_t th_low, const uint8_t* d_q_skip, int32_t* d_best_kp,
+                    int32_t* d_best_dist, uint8_t* d_epi_ok, void* stream) {
+  int rc = fuse::check_args(rule, tg, q);
+  if (rc) return rc;
+  const int64_t nw = (int64_t)tg->n_targets * q->nq * tg->n_cams;
+  if (nw == 0) return MCS_OK;
+  if (!d_best_kp || !d_best_dist || (rule == 0 && !d_epi_ok) || !tg->cell_ptr ||
+      (tg->n_kp_total > 0 && !tg->cell_kp)) {
+    set_error("fuse: null device buffer");
+    return MCS_ERR_ARG;
+  }
+  if (ws && tg->n_targets > ws->max_targets) {
+    set_error("fuse: more targets than the workspace holds");
+    return MCS_ERR_ARG;
+  }
+  mcs_fuse_workspace* tmp = nullptr;
+  if (!ws) {
+    int dev = 0;
+    MCS_HIP_CHECK(hipGetDevice(&dev));
+    rc = mcs_fuse_workspace_create(dev, tg->n_targets, &tmp);
+    if (rc) return rc;
+    ws = tmp;
+  } else {
+    MCS_HIP_CHECK(hipSetDevice(ws->device));
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int tc = tg->n_targets * tg->n_cams;
+  hipLaunchKernelGGL(fuse::k_fuse_setup, dim3((tc + 63) / 64), dim3(64), 0, st, tg->m_t, tg->m_c,
+                     q->m_t, tg->n_targets, tg->n_cams, rule, ws->Rt, ws->E);
+  fuse::Args a{tg->n_targets, q->nq, tg->n_cams, tg->bytes, tg->n_levels, tg->mirror_w, tg->mirror_h,
+               tg->n_kp_total, rule, (rule != 1 || (flags & MCS_FUSE_USE_DISTANCE)) ? 1 : 0, th_low,
+               th, tg->off, tg->kp_xy, tg->kp_octave, tg->desc, tg->mask, tg->rays, tg->m_t, tg->cam,
+               tg->mirror, tg->grid_params, tg->scale, tg->cell_ptr, tg->cell_kp, q->pos, q->dist,
+               q->desc, q->mask, q->rays, ws->Rt, ws->E, d_q_skip, d_best_kp, d_best_dist,
+               rule == 0 ? d_epi_ok : nullptr};
+  hipLaunchKernelGGL(fuse::k_fuse, dim3((unsigned)((nw + fuse::kWPB - 1) / fuse::kWPB)), dim3(256), 0,
+                     st, a);
+  hipError_t e = hipGetLastError();
+  if (tmp) {
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    mcs_fuse_workspace_destroy(tmp);
+  }
+  MCS_HIP_CHECK(e);
+  return MCS_OK;
+}
+
+int mcs_fuse(int32_t device, int32_t rule, int32_t flags, const mcs_fuse_targets* tg,
+             const mcs_fuse_queries* q, double th, int32_t th_low, const uint8_t* q_skip,
+             int32_t* best_kp, int32_t* best_dist, uint8_t* epi_ok) {
+  int rc = fuse::check_args(rule, tg, q);
+  if (rc) return rc;
+  const int T = tg->n_targets, C = tg->n_cams, nq = q->nq;
+  const size_t nw = (size_t)T * nq * C;
+  if (nw == 0) return MCS_OK;
+  if (!best_kp || !best_dist || (rule == 0 && !epi_ok) || (tg->n_kp_total > 0 && !tg->kp_cam)) {
+    set_error("fuse: null host buffer");
+    return MCS_ERR_ARG;
+  }
+  if (tg->off[0] != 0 || tg->off[T] != tg->n_kp_total) { set_error("fuse: off[0] must be 0 and off[n_targets] n_kp_total"); return MCS_ERR_ARG; }
+  for (int t = 0; t < T; t++) {
+    if (tg->off[t + 1] < tg->off[t]) { set_error("fuse: offsets must be non-decreasing"); return MCS_ERR_ARG; }
+    if (tg->off[t + 1] - tg->off[t] >= fuse::kMaxKpPerTarget) {
+      set_error("fuse: keypoints per target must be below 2^19 (position field of the key)");
+      return MCS_ERR_ARG;
+    }
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+    set_error("no HIP device visible (no CPU fallback)");
+    return MCS_ERR_NO_DEVICE;
+  }
+  if (device < 0 || device >= ndev) { set_error("fuse: no such device"); return MCS_ERR_ARG; }
+  MCS_HIP_CHECK(hipSetDevice(device));
+  const size_t ncell = (size_t)C * win::kCols * win::kRows, nk = (size_t)tg->n_kp_total, nb = (size_t)tg->bytes;
+  std::vector<int32_t> cell_ptr((size_t)T * (ncell + 1)), cell_kp(std::max<size_t>(1, nk), 0);
+  for (int t = 0; t < T; t++) {
+    const size_t o = (size_t)tg->off[t];
+    rc = mcs_frame_grid_build(tg->kp_xy ? tg->kp_xy + 2 * o : nullptr, tg->kp_cam ? tg->kp_cam + o : nullptr,
+                              tg->off[t + 1] - tg->off[t], C, tg->grid_params,
+                              cell_ptr.data() + (size_t)t * (ncell + 1), cell_kp.data() + o, nullptr);
+    if (rc) { set_error("fuse: grid build failed"); return rc; }
+  }
+  fuse::DevBufs B;
+  mcs_fuse_targets d = *tg;
+  d.off = B.up(tg->off, (size_t)T + 1);
+  d.kp_xy = B.up(tg->kp_xy, 2 * nk);
+  d.kp_octave = B.up(tg->kp_octave, nk);
+  d.kp_cam = nullptr;
+  d.desc = B.up(tg->desc, nk * nb);
+  d.mask = tg->mask ? B.up(tg->mask, nk * nb) : nullptr;
+  d.rays = rule == 0 ? B.up(tg->rays, 3 * nk) : nullptr;
+  d.m_t = B.up(tg->m_t, 16 * (size_t)T);
+  d.m_c = B.up(tg->m_c, 16 * (size_t)C);
+  d.cam = B.up(tg->cam, 17 * (size_t)C);
+  d.mirror = B.up(tg->mirror, (size_t)C * tg->mirror_w * tg->mirror_h);
+  d.grid_params = B.up(tg->grid_params, 4 * (size_t)C);
+  d.scale = B.up(tg->scale, (size_t)tg->n_levels);
+  d.cell_ptr = B.up(cell_ptr.data(), cell_ptr.size());
+  d.cell_kp = B.up(cell_kp.data(), cell_kp.size());
+  mcs_fuse_queries dq = *q;
+  dq.pos = B.up(q->pos, 3 * (size_t)nq);
+  dq.dist = B.up(q->dist, 2 * (size_t)nq);
+  dq.desc = B.up(q->desc, (size_t)nq * nb);
+  dq.mask = q->mask ? B.up(q->mask, (size_t)nq * nb) : nullptr;
+  dq.rays = rule == 0 ? B.up(q->rays, 3 * (size_t)nq) : nullptr;
+  dq.m_t = rule == 0 ? B.up(q->m_t, 16) : nullptr;
+  const uint8_t* d_skip = q_skip ? B.up(q_skip, (size_t)T * nq) : nullptr;
+  int32_t* d_bk = B.alloc<int32_t>(nw);
+  int32_t* d_bd = B.alloc<int32_t>(nw);
+  uint8_t* d_ep = rule == 0 ? B.alloc<uint8_t>(nw) : nullptr;
+  if (B.err != hipSuccess) { set_hip_error(B.err, "fuse upload", __FILE__, __LINE__); return MCS_ERR_HIP; }
+  rc = mcs_fuse_device(nullptr, rule, flags, &d, &dq, th, th_low, d_skip, d_bk, d_bd, d_ep, nullptr);
+  if (rc) return rc;
+  MCS_HIP_CHECK(hipMemcpy(best_kp, d_bk, 4 * nw, hipMemcpyDeviceToHost));
+  MCS_HIP_CHECK(hipMemcpy(best_dist, d_bd, 4 * nw, hipMemcpyDeviceToHost));
+  if (rule == 0) MCS_HIP_CHECK(hipMemcpy(epi_ok, d_ep, nw, hipMemcpyDeviceToHost));
+  return MCS_OK;
+}
+
+}  // extern "C"

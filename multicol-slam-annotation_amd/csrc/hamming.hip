@@ -5,6 +5,7 @@
 //            SearchForTriangulationRaw          src/cORBmatcher.cpp:968-1156
 //            best/second-best scans             src/cORBmatcher.cpp:67-163, 326-475
 #include "common.hpp"
+#include "proj_window.hpp"
 #include "ham_dist.hpp"
 #include <map>
 #include <mutex>
@@ -458,23 +459,8 @@ int mcs_hamming_top2_batch_device(const uint8_t* d_desc, const int32_t* d_counts
 
 namespace mcs {
 
-// CheckDistEpipolarLine (src/misc.cpp:54-70).  nom = (ray2^T E12) ray1 evaluated left to right
-// as cv::Matx does; (ray2^T E12)_c = sum_r ray2_r E_rc is exactly Etx2_c, so nom = Etx2 . ray1.
-// One definition for the host entry and the device search (same operation order, no FMA
-// contraction on either side: -ffp-contract=off), so both give the same verdict bit for bit.
-__host__ __device__ __forceinline__ bool epi_check(const double* r1, const double* r2,
-                                                   const double* Em, double thresh) {
-  double Ex1[3], Etx2[3];
-  for (int r = 0; r < 3; r++) {
-    Ex1[r] = Em[3 * r] * r1[0] + Em[3 * r + 1] * r1[1] + Em[3 * r + 2] * r1[2];
-    Etx2[r] = r2[0] * Em[r] + r2[1] * Em[3 + r] + r2[2] * Em[6 + r];
-  }
-  const double nom = Etx2[0] * r1[0] + Etx2[1] * r1[1] + Etx2[2] * r1[2];
-  const double den = Ex1[0] * Ex1[0] + Ex1[1] * Ex1[1] + Ex1[2] * Ex1[2] + Etx2[0] * Etx2[0] +
-                     Etx2[1] * Etx2[1] + Etx2[2] * Etx2[2];
-  if (den == 0.0) return false;
-  return (nom * nom) / den < thresh;
-}
+// CheckDistEpipolarLine (src/misc.cpp:54-70) is epi_check of proj_window.hpp: one definition for
+// the host entry and the device searches.
 
 // ---- SearchForTriangulationRaw on the device (src/cORBmatcher.cpp:1016-1089)
 // The reference walks KF1's keypoints in index order; for each it sorts the (dist, idx2) list of

@@ -14,7 +14,7 @@
 // checkOrientation is false in the reference (include/cORBmatcher.h:40), so no rotation
 // histograms.  GetFeaturesInArea's abs(kp.pt.x - x) is the double overload (the operand is a
 // double), i.e. fabs.
-#include "common.hpp"
+#include "proj_window.hpp"
 #include "../../include/mcs_matcher.h"
 #include <algorithm>
 #include <climits>
@@ -24,7 +24,6 @@
 namespace mcs {
 namespace win {
 
-constexpr int kCols = MCS_GRID_COLS, kRows = MCS_GRID_ROWS;
 constexpr int kQPB = 4;   // queries (waves) per 256-thread workgroup
 
 struct SearchArgs {
@@ -34,47 +33,6 @@ struct SearchArgs {
   const double* q_xyr; const int32_t* q_cl; const uint8_t* q_desc; const uint8_t* q_mask;
   int32_t* cand_ptr; int32_t* cand_kp; int32_t* cand_dist;
 };
-
-// window cell range of GetFeaturesInArea (:280-298); false = empty window
-__device__ __forceinline__ bool cell_range(const SearchArgs& a, int cam, double x, double y,
-                                           double r, int* x0, int* x1, int* y0, int* y1) {
-  const double mnx = a.gp[4 * cam], mny = a.gp[4 * cam + 1];
-  const double wi = a.gp[4 * cam + 2], hi = a.gp[4 * cam + 3];
-  int nx0 = (int)floor((x - mnx - r) * wi);
-  nx0 = max(0, nx0);
-  if (nx0 >= kCols) return false;
-  int nx1 = (int)ceil((x - mnx + r) * wi);
-  nx1 = min(kCols - 1, nx1);
-  if (nx1 < 0) return false;
-  int ny0 = (int)floor((y - mny - r) * hi);
-  ny0 = max(0, ny0);
-  if (ny0 >= kRows) return false;
-  int ny1 = (int)ceil((y - mny + r) * hi);
-  ny1 = min(kRows - 1, ny1);
-  if (ny1 < 0) return false;
-  *x0 = nx0; *x1 = nx1; *y0 = ny0; *y1 = ny1;
-  return true;
-}
-
-// DescriptorDistance64 / ...Masked over 32-bit words (the masked total is halved once, as
-// the reference does over its 64-bit words)
-__device__ __forceinline__ int ham(const uint8_t* q, const uint8_t* t, const uint8_t* mq,
-                                  const uint8_t* mt, int bytes) {
-  const uint32_t* a = reinterpret_cast<const uint32_t*>(q);
-  const uint32_t* b = reinterpret_cast<const uint32_t*>(t);
-  int d = 0;
-  if (!mq) {
-    for (int w = 0; w < bytes / 4; w++) d += __popc(a[w] ^ b[w]);
-    return d;
-  }
-  const uint32_t* ma = reinterpret_cast<const uint32_t*>(mq);
-  const uint32_t* mb = reinterpret_cast<const uint32_t*>(mt);
-  for (int w = 0; w < bytes / 4; w++) {
-    const uint32_t x = a[w] ^ b[w];
-    d += __popc(x & ma[w]) + __popc(x & mb[w]);
-  }
-  return d / 2;
-}
 
 // One wave per query.  The window's cells are taken 64 at a time, one per lane in the
 // reference's loop order (ix outer, iy inner); a wave prefix sum over the cell sizes flattens
@@ -91,7 +49,7 @@ __global__ __launch_bounds__(256) void k_window(SearchArgs a) {
   const int cam = a.q_cl[3 * q], minL = a.q_cl[3 * q + 1], maxL = a.q_cl[3 * q + 2];
   int cnt = 0;
   int x0, x1, y0, y1;
-  if (cam >= 0 && cam < a.n_cams && cell_range(a, cam, x, y, r, &x0, &x1, &y0, &y1)) {
+  if (cam >= 0 && cam < a.n_cams && cell_range(a.gp + 4 * cam, x, y, r, &x0, &x1, &y0, &y1)) {
     const bool check = !(minL == -1 && maxL == -1);
     const bool same = check && (minL == maxL);
     const uint8_t* qd = a.q_desc + (int64_t)q * a.bytes;

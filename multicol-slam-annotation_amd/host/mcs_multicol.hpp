@@ -368,4 +368,147 @@ inline std::vector<int> SearchByBoW(const BowFrame& KF1, const std::vector<const
   return std::vector<int>(n.begin(), n.begin() + kf2s.size());
 }
 
+// cORBmatcher::Fuse, the three overloads (src/cORBmatcher.cpp:1265-1418 rule 0, :1420-1567 rule 1,
+// :1570-1719 rule 2): one set of map points against a batch of target keyframes.  The device does
+// the projection / window / best-distance part for all targets in one call (mcs_fuse); the tails
+// run target by target on the host (mcs_fuse_select) against the caller's map, reached through
+// the FuseMap callbacks.
+struct FuseRig {                    // what all keyframes of the rig share
+  int n_cams = 0, mirror_w = 0, mirror_h = 0;
+  std::vector<double> m_c;          // [n_cams][16] M_c row-major
+  std::vector<double> cam;          // [n_cams][17] c d e u0 v0 invP[12]
+  std::vector<uint8_t> mirror;      // [n_cams][mirror_h][mirror_w] mirrorMasks[0]
+  std::vector<double> grid_params;  // [n_cams][4] mnMinX mnMinY mfGridElementWidthInv ...HeightInv
+  std::vector<double> scale;        // mvScaleFactors
+};
+struct FuseKeyFrame {               // a target keyframe as flat arrays
+  std::vector<float> kp_xy;         // [n][2] mvKeys pt
+  std::vector<int32_t> kp_octave, kp_cam;
+  std::vector<uint8_t> desc, mask;  // [n][bytes]; mask empty or mdBRIEF masks
+  std::vector<double> rays;         // [n][3] GetKeyPointRay (rule 0)
+  double m_t[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // Get_M_t(); rule 2: FuseSim3ToMt(Scw)
+};
+struct FusePoints {                 // the query map points (vpMapPoints / vpPoints)
+  std::vector<int32_t> mp;          // map-point id per query, -1 = NULL
+  std::vector<double> pos, dist;    // [nq][3] GetWorldPos, [nq][2] mfMinDistance mfMaxDistance
+  std::vector<uint8_t> desc, mask;  // [nq][bytes]
+  std::vector<double> rays;         // rule 0: [nq][3] curKF->GetKeyPointRay(i)
+  double cur_m_t[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // rule 0: curKF Get_M_t()
+};
+struct FuseAction { int32_t kind, query, keypoint, other; };   // mcs_fuse_select's action rows
+struct FuseMap {
+  int n_mp = 0;
+  // the state of target t as mcs_fuse_select takes it: isBad per map point, IsInKeyFrame(target)
+  // per map point, the target's mvpMapPoints as ids
+  virtual void state(int t, std::vector<uint8_t>& mp_bad, std::vector<uint8_t>& mp_in_kf,
+                     std::vector<int32_t>& kp_mp) = 0;
+  // after target t's tail: the updated state and the ordered actions, to replay onto the map
+  // (AddObservation + AddMapPoint, Replace with its effect on the other keyframes)
+  virtual void apply(int t, const std::vector<FuseAction>& actions, const std::vector<uint8_t>& mp_bad,
+                     const std::vector<uint8_t>& mp_in_kf, const std::vector<int32_t>& kp_mp) = 0;
+  // the descriptor (and mask) of map point mp after ComputeDistinctiveDescriptors
+  // (src/cMapPoint.cpp:244), written into the query's rows
+  virtual void descriptor(int mp, uint8_t* desc, uint8_t* mask) = 0;
+  virtual ~FuseMap() {}
+};
+
+// Rule 2's pose from Scw (:1576-1585): M_t = invMat(Rt2Hom(sRcw / s, tcw / s)), the reference's
+// operation order (dot and Matx products accumulate s = 0; s += a * b in index order).
+inline void FuseSim3ToMt(const double* Scw, double* Mt) {
+  double dot = 0;
+  for (int j = 0; j < 3; j++) dot += Scw[j] * Scw[j];
+  const double inv = 1.0 / std::sqrt(dot);
+  double R[9], t[3];
+  for (int i = 0; i < 3; i++) {
+    for (int j = 0; j < 3; j++) R[3 * i + j] = Scw[4 * i + j] * inv;
+    t[i] = Scw[4 * i + 3] * inv;
+  }
+  for (int i = 0; i < 3; i++) {
+    double s = 0;
+    for (int k = 0; k < 3; k++) {
+      Mt[4 * i + k] = R[3 * k + i];
+      s += (R[3 * k + i] * -1.0) * t[k];
+    }
+    Mt[4 * i + 3] = s;
+  }
+  Mt[12] = Mt[13] = Mt[14] = 0.0;
+  Mt[15] = 1.0;
+}
+
+// Returns nFused per target.  When a Replace survivor is itself a query its descriptor changes
+// (batch contract of include/mcs_matcher.h): its rows are refreshed through map.descriptor and
+// the remaining targets are run again.  th: 2.5 (rule 0 in SearchInNeighbors), 3.0 (rule 1) or
+// the caller's; th_low = the matcher's TH_LOW_.
+inline std::vector<int> Fuse(int rule, const FuseRig& rig, const std::vector<const FuseKeyFrame*>& targets,
+                             FusePoints& pts, int bytes, double th, int th_low, FuseMap& map, int flags = 0,
+                             int device = 0) {
+  const int T = (int)targets.size(), C = rig.n_cams, nq = (int)pts.mp.size();
+  std::vector<int> n_fused(T, 0);
+  const bool masked = !pts.mask.empty();
+  std::vector<uint8_t> bad, in_kf;
+  std::vector<int32_t> kp_mp;
+  for (int t0 = 0; t0 < T;) {
+    const int nt = T - t0;
+    std::vector<int32_t> off(1, 0), oct, cam;
+    std::vector<float> xy;
+    std::vector<uint8_t> desc, mask, skip((size_t)nt * nq, 0);
+    std::vector<double> rays, m_t;
+    for (int t = t0; t < T; t++) {
+      const FuseKeyFrame& k = *targets[t];
+      if (masked != !k.mask.empty()) throw std::invalid_argument("Fuse: masks for the points and every keyframe or none");
+      off.push_back(off.back() + (int32_t)k.kp_octave.size());
+      xy.insert(xy.end(), k.kp_xy.begin(), k.kp_xy.end());
+      oct.insert(oct.end(), k.kp_octave.begin(), k.kp_octave.end());
+      cam.insert(cam.end(), k.kp_cam.begin(), k.kp_cam.end());
+      desc.insert(desc.end(), k.desc.begin(), k.desc.end());
+      mask.insert(mask.end(), k.mask.begin(), k.mask.end());
+      rays.insert(rays.end(), k.rays.begin(), k.rays.end());
+      m_t.insert(m_t.end(), k.m_t, k.m_t + 16);
+      map.state(t, bad, in_kf, kp_mp);   // the skip snapshot: these conditions only grow
+      std::vector<uint8_t> found;
+      if (rule == 2) {
+        found.assign(map.n_mp, 0);
+        for (int32_t m : kp_mp) if (m >= 0 && !bad[m]) found[m] = 1;
+      }
+      for (int i = 0; i < nq; i++) {
+        const int m = pts.mp[i];
+        skip[(size_t)(t - t0) * nq + i] = m < 0 || bad[m] || (rule == 2 ? found[m] : in_kf[m]);
+      }
+    }
+    mcs_fuse_targets tg{nt, off.back(), C, bytes, (int32_t)rig.scale.size(), rig.mirror_w, rig.mirror_h,
+                        off.data(), xy.data(), oct.data(), cam.data(), desc.data(),
+                        masked ? mask.data() : nullptr, rule == 0 ? rays.data() : nullptr, m_t.data(),
+                        rig.m_c.data(), rig.cam.data(), rig.mirror.data(), rig.grid_params.data(),
+                        rig.scale.data(), nullptr, nullptr};
+    mcs_fuse_queries q{nq, pts.pos.data(), pts.dist.data(), pts.desc.data(), masked ? pts.mask.data() : nullptr,
+                       rule == 0 ? pts.rays.data() : nullptr, rule == 0 ? pts.cur_m_t : nullptr};
+    const size_t per = (size_t)nq * C;
+    std::vector<int32_t> bk(nt * per + 1), bd(nt * per + 1), req(nq + 1);
+    std::vector<uint8_t> ep(nt * per + 1);
+    check(mcs_fuse(device, rule, flags, &tg, &q, th, th_low, skip.data(), bk.data(), bd.data(), ep.data()), "mcs_fuse");
+    int next = T;
+    for (int t = t0; t < T; t++) {
+      map.state(t, bad, in_kf, kp_mp);
+      std::vector<FuseAction> act(per + 1);
+      int32_t na = 0, nf = 0, nr = 0;
+      check(mcs_fuse_select(rule, nq, C, pts.mp.data(), bk.data() + (t - t0) * per, ep.data() + (t - t0) * per,
+                            map.n_mp, bad.data(), in_kf.data(), (int32_t)kp_mp.size(), kp_mp.data(),
+                            &act[0].kind, (int32_t)per, &na, &nf, req.data(), &nr), "mcs_fuse_select");
+      act.resize(na);
+      n_fused[t] = nf;
+      map.apply(t, act, bad, in_kf, kp_mp);
+      if (nr > 0 && t + 1 < T) {   // refresh the survivors' rows, run the remaining targets again
+        for (int r = 0; r < nr; r++)
+          for (int i = 0; i < nq; i++)
+            if (pts.mp[i] == req[r])
+              map.descriptor(req[r], &pts.desc[(size_t)i * bytes], masked ? &pts.mask[(size_t)i * bytes] : nullptr);
+        next = t + 1;
+        break;
+      }
+    }
+    t0 = next;
+  }
+  return n_fused;
+}
+
 }  // namespace mcs

@@ -162,6 +162,13 @@ SIGNATURES = {
     "mcs_search_by_bow": (ctypes.c_int, [_I32, _P, _P, _I32, _I32, ctypes.c_double, _I32, _P, _P]),
     "mcs_search_by_bow_kf_device": (ctypes.c_int, [_P, _P, _P, _I32, _I32, ctypes.c_double, _P, _P, _P]),
     "mcs_search_by_bow_kf": (ctypes.c_int, [_I32, _P, _P, _I32, _I32, ctypes.c_double, _P, _P]),
+    # Fuse (include/mcs_matcher.h; wrappers in mcs_amd/fuse.py)
+    "mcs_fuse_workspace_create": (ctypes.c_int, [_I32, _I32, _P]),
+    "mcs_fuse_workspace_destroy": (None, [_P]),
+    "mcs_fuse_device": (ctypes.c_int, [_P, _I32, _I32, _P, _P, ctypes.c_double, _I32, _P, _P, _P, _P, _P]),
+    "mcs_fuse": (ctypes.c_int, [_I32, _I32, _I32, _P, _P, ctypes.c_double, _I32, _P, _P, _P, _P]),
+    "mcs_fuse_select": (ctypes.c_int, [_I32, _I32, _I32, _P, _P, _P, _I32, _P, _P, _I32, _P, _P, _I32,
+                                       _P, _P, _P, _P]),
     # DBoW2 vocabulary (include/mcs_vocab.h)
     "mcs_vocab_create": (_I32, [_I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _P, _I32, _P]),
     "mcs_vocab_destroy": (_I32, [_P]),
