@@ -472,11 +472,7 @@ struct LmEnd { double* sc; const int* flag; LmSig* sig; uint64_t seq; LmCtl* hos
 #ifndef MCS_LM_AHEAD
 #define MCS_LM_AHEAD 2      // LM steps the host keeps enqueued ahead of the device
 #endif
-#ifndef MCS_EXP_PUB_DONE
-#define MCS_EXP_PUB_DONE 0  // experiment builds: publish progress only once the run is done
-#endif
 __device__ __forceinline__ void lm_publish(const LmCtl* c, const LmEnd& le) {
-  if (MCS_EXP_PUB_DONE && !c->done) return;
   // relaxed: a stale `done` only costs the host one more (no-op) step
   __hip_atomic_store(&le.sig->done, c->done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   __hip_atomic_store(&le.sig->iter, c->iter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

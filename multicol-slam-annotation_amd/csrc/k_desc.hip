@@ -130,18 +130,12 @@ __device__ __forceinline__ uint32_t load_aligned_dword(const uint8_t* g) {
 }
 
 // Blurred patch (+-21 around the keypoint) staged in LDS rows of kBlrRow bytes, one 16-byte
-// chunk per load.  Default (round 6): the chunks start at the dword below the patch (mis =
-// (cx - 21) & 3; global loads need dword alignment only), so 3 chunks cover a row's 43 + 3
-// bytes: 48-byte LDS rows, 129 chunks per keypoint (5 loads per lane), 2064 B per keypoint.
-// MCS_DESC_ROW64 (the round-2..5 layout): 16-byte aligned chunks (mis = (cx - 21) & 15), 4
-// per row, 64-byte rows, 172 chunks (6 loads per lane), 2752 B per keypoint.  A/B in round 6:
-// 0.575 (48-byte rows: 20.9 KB per workgroup, 7 per CU) against 0.577 ms (26.4 KB, 6 per CU).
-// (Measured slower in round 2: 12 dword loads per 48-byte row, 1.11 vs 0.89 ms.)
-#ifdef MCS_DESC_ROW64
-constexpr int kBlrRow = 64, kBlrAlign = 15;
-#else
+// chunk per load.  The chunks start at the dword below the patch (mis = (cx - 21) & 3; global
+// loads need dword alignment only), so 3 chunks cover a row's 43 + 3 bytes: 48-byte LDS rows,
+// 129 chunks per keypoint (5 loads per lane), 2064 B per keypoint.  The layout this replaced
+// (16-byte aligned chunks, 64-byte rows, 2752 B per keypoint) measured 0.577 ms against 0.575
+// in round 6 (6 against 7 workgroups per CU).
 constexpr int kBlrRow = 48, kBlrAlign = 3;
-#endif
 constexpr int kBlrChunks = kBlrRow / 16;   // 16-byte chunks per row
 
 // sum over each 32-lane half of the wave (exact integers, any order): xor 1 and 2 (quad_perm),

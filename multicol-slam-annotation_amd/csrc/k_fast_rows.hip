@@ -31,6 +31,35 @@
 
 namespace mcs {
 
+// Instrumentation switch, off in the product (the macros expand to nothing).  A variant library
+// built with -DMCS_FAST_PROBE (tools/build_variants.sh) is read by tools/gpu/fast_probe.py;
+// tests/test_probe_builds.py compiles it.  Shader cycles per phase summed over all waves:
+// [0] band loads + ring writes, [1] compass + list, [2] exact test + score, [3] NMS + mask +
+// append, [4] whole wave, [5] bands, [6] skipped (fully masked) bands, [7] setup before the
+// first band.
+#ifdef MCS_FAST_PROBE
+__device__ unsigned long long g_fast_probe[8];
+extern "C" int mcs_debug_fast_probe(unsigned long long* out, int reset) {
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fast_probe), sizeof(g_fast_probe)) != hipSuccess) return -1;
+  if (reset) {
+    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_fast_probe), z, sizeof(z)) != hipSuccess) return -1;
+  }
+  return 0;
+}
+#define FP_BEGIN() unsigned long long acc_[8] = {0, 0, 0, 0, 0, 0, 0, 0}; \
+  const long long t_begin_ = __builtin_amdgcn_s_memtime()
+#define FP_T(v) const long long v = __builtin_amdgcn_s_memtime()
+#define FP_ADD(k, v) (acc_[k] += (unsigned long long)(v))
+#define FP_END() do { FP_ADD(4, __builtin_amdgcn_s_memtime() - t_begin_); \
+    if (lane == 0) for (int k = 0; k < 8; k++) atomicAdd(&g_fast_probe[k], acc_[k]); } while (0)
+#else
+#define FP_BEGIN() do { } while (0)
+#define FP_T(v) do { } while (0)
+#define FP_ADD(k, v) do { } while (0)
+#define FP_END() do { } while (0)
+#endif
+
 namespace {
 #ifndef MCS_FAST_BAND
 #define MCS_FAST_BAND 5
@@ -101,19 +130,6 @@ __device__ __forceinline__ int fast_small(const uint8_t* lds, uint32_t ring_base
 }
 }  // namespace
 
-// Tuning probe (tools/gpu/fast_probe.py, variant builds with -DMCS_FAST_PROBE only): shader
-// cycles per phase summed over all waves: [0] band loads + ring writes, [1] compass + list,
-// [2] exact test + score, [3] NMS + mask + append, [4] whole wave, [5] bands, [6] skipped
-// (fully masked) bands, [7] setup before the first band.
-#ifdef MCS_FAST_PROBE
-__device__ unsigned long long g_fast_probe[8];
-#define FP_T(v) const long long v = __builtin_amdgcn_s_memtime()
-#define FP_ADD(k, v) (acc_[k] += (unsigned long long)(v))
-#else
-#define FP_T(v) do { } while (0)
-#define FP_ADD(k, v) do { } while (0)
-#endif
-
 template <int PAT>
 __global__ __launch_bounds__(256) void k_fast_rows(FastRowArgs a) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[kLdsBytes];
@@ -140,10 +156,7 @@ __global__ __launch_bounds__(256) void k_fast_rows(FastRowArgs a) {
   auto zero_count = [&] { if (ui == 0 && lane == 0) a.frame_count[f] = 0; };
   const int mi = a.mask_index ? min(max(a.mask_index[f], 0), a.nmasks - 1) : 0;
   const FastUnit u = a.units[(int64_t)mi * a.unit_mstride + ui];
-#ifdef MCS_FAST_PROBE
-  unsigned long long acc_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  const long long t_begin_ = __builtin_amdgcn_s_memtime();
-#endif
+  FP_BEGIN();
   const int level = u.level, nc = u.ncells, wh = u.wy1 - u.wy0;
   int32_t* const cnt_out = a.cell_counts + (int64_t)f * a.ncells + u.cell0;
   if (wh <= 0) {
@@ -217,9 +230,7 @@ __global__ __launch_bounds__(256) void k_fast_rows(FastRowArgs a) {
 
   const int nbands = (wh + kBand - 1) / kBand;
   int ncarry = 0;   // corners of the previous band's last row, at the front of the list
-#ifdef MCS_FAST_PROBE
   FP_ADD(7, __builtin_amdgcn_s_memtime() - t_begin_);
-#endif
   for (int b = 0; b < nbands; b++) {
     FP_T(t0_);
     const int y0 = 3 + b * kBand, y1 = min(y0 + kBand, 3 + wh);
@@ -271,9 +282,7 @@ __global__ __launch_bounds__(256) void k_fast_rows(FastRowArgs a) {
       for (int i = 0; i < kBand + 2; i++) any |= m[i];
       if (__ballot(any != 0) == 0) {
         ncarry = 0;
-#ifdef MCS_FAST_PROBE
         FP_ADD(6, __builtin_amdgcn_s_memtime() - t0_);
-#endif
         continue;
       }
     }
@@ -493,23 +502,8 @@ __global__ __launch_bounds__(256) void k_fast_rows(FastRowArgs a) {
   }
   if (lane < nc) cnt_out[lane] = cnt;
   zero_count();
-#ifdef MCS_FAST_PROBE
-  acc_[4] += (unsigned long long)(__builtin_amdgcn_s_memtime() - t_begin_);
-  if (lane == 0)
-    for (int k = 0; k < 8; k++) atomicAdd(&g_fast_probe[k], acc_[k]);
-#endif
+  FP_END();
 }
-
-#ifdef MCS_FAST_PROBE
-extern "C" int mcs_debug_fast_probe(unsigned long long* out, int reset) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fast_probe), sizeof(g_fast_probe)) != hipSuccess) return -1;
-  if (reset) {
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_fast_probe), z, sizeof(z)) != hipSuccess) return -1;
-  }
-  return 0;
-}
-#endif
 
 void launch_fast_rows(const FastRowArgs& a_in, hipStream_t st) {
   // (pattern 12 / 8: the compare constants are unused)

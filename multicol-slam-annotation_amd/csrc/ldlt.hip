@@ -28,6 +28,48 @@ namespace ldlt {
 
 namespace {
 
+// Instrumentation switches, off in the product (the macros expand to nothing).  Each is turned
+// on by the tool that includes this file; tests/test_probe_builds.py compiles all of them.
+//   MCS_LDLT_PROBE (tools/bench/ldlt_probe.hip, tools/bench/ldlt_solve_probe.hip): phase clocks
+//     of factor_tile [9], of k_panel per (step, workgroup) [k][wg][8] (s_memtime), and of k_pipe
+//     per diag step [k][8] and per task [ticket][4] (s_memrealtime, 100 MHz).
+//   MCS_PIPE_TRACE (tools/bench/pipe_debug.hip): k_pipe events {wg, code, a, b} into host memory.
+#ifdef MCS_LDLT_PROBE
+__device__ long long g_ldlt_stamps[16];
+__device__ long long g_panel_stamps[32 * 256 * 8];
+__device__ long long g_diag_stamps[128 * 8];
+__device__ long long g_task_stamps[65536 * 4];
+#define LDLT_STAMP(i) do { if (threadIdx.x == 0) g_ldlt_stamps[i] = __builtin_amdgcn_s_memtime(); } while (0)
+#define PANEL_STAMP(i) do { if (threadIdx.x == 0 && k < 32 && blockIdx.x < 256) \
+    g_panel_stamps[((size_t)k * 256 + blockIdx.x) * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
+#define DSTAMP(k, i) do { if (threadIdx.x == 0 && (k) < 128) g_diag_stamps[(k) * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#define TSTAMP(tk, i) do { if (threadIdx.x == 0 && (tk) < 65536) g_task_stamps[(tk) * 4 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#else
+#define LDLT_STAMP(i) do { } while (0)
+#define PANEL_STAMP(i) do { } while (0)
+#define DSTAMP(k, i) do { } while (0)
+#define TSTAMP(tk, i) do { } while (0)
+#endif
+#ifdef MCS_PIPE_TRACE
+__device__ unsigned* g_pipe_trace;
+__device__ unsigned g_pipe_trace_n;
+__device__ __forceinline__ void ptrace(unsigned code, unsigned a, unsigned b) {
+  if (threadIdx.x == 0 && g_pipe_trace) {
+    const unsigned i = atomicAdd(&g_pipe_trace_n, 1u);
+    if (i < 65536) {
+      unsigned* e = g_pipe_trace + 4 * (size_t)i;
+      __hip_atomic_store(e + 1, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(e + 2, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(e + 3, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(e + 0, blockIdx.x + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+#define PTRACE(c, a, b) ptrace((c), (unsigned)(a), (unsigned)(b))
+#else
+#define PTRACE(c, a, b) do { } while (0)
+#endif
+
 // LDS row stride in doubles.  66 = 2 (mod 32): the MFMA operand reads (lane (r, k) of a
 // 16 x 4 sub-block at r * LS + k) hit 32 distinct bank pairs per half-wave (conflict-free);
 // the row-per-lane accesses of the panel elimination are 2-way.
@@ -62,23 +104,12 @@ __device__ __forceinline__ void put_tile_lower(double* s, const d2 (&v)[8]) {
     *reinterpret_cast<d2*>(&s[r * LS + c]) = w;
   }
 }
+// (used by tools/bench/ldlt_probe.hip only)
 __device__ __forceinline__ void load_tile_lower(double* s, const double* __restrict__ g) {
   d2 v[8];
   fetch_tile(v, g);
   put_tile_lower(s, v);
 }
-
-#ifdef MCS_LDLT_PROBE
-__device__ long long g_ldlt_stamps[16];
-#define LDLT_STAMP(i) do { if (threadIdx.x == 0) g_ldlt_stamps[i] = __builtin_amdgcn_s_memtime(); } while (0)
-// per (step, workgroup) phase clocks of k_panel: [k][wg][8]
-__device__ long long g_panel_stamps[32 * 256 * 8];
-#define PANEL_STAMP(i) do { if (threadIdx.x == 0 && k < 32 && blockIdx.x < 256) \
-    g_panel_stamps[((size_t)k * 256 + blockIdx.x) * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define LDLT_STAMP(i) do { } while (0)
-#define PANEL_STAMP(i) do { } while (0)
-#endif
 
 __device__ __forceinline__ double readlane_d(double v, int l) {
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
@@ -103,29 +134,6 @@ __device__ __forceinline__ void inv_diag16(const double* sA, double* sI, int B) 
 #pragma unroll
     for (int r = 0; r < 16; r++) sI[(B + r) * LS + B + c] = x[r];
   }
-}
-
-// off-diagonal block X_ij = -X_ii (sum_{k=j}^{i-1} L_ik X_kj) of L^-1 (one wave, MFMA); the
-// inner sum stays in accumulator layout, which is the B-operand layout of the outer product
-__device__ __forceinline__ void offdiag_block(const double* sA, double* sI, int i, int j) {
-  const int l = threadIdx.x & 63, r16 = l & 15, k4 = l >> 4;
-  d4 s = {0.0, 0.0, 0.0, 0.0};
-  for (int k = j; k < i; k++) {
-#pragma unroll
-    for (int k0 = 0; k0 < 16; k0 += 4) {
-      const double av = sA[(16 * i + r16) * LS + 16 * k + k0 + k4];   // L_ik[m][kk]
-      const double bv = sI[(16 * k + k0 + k4) * LS + 16 * j + r16];   // X_kj[kk][n]
-      s = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, s, 0, 0, 0);
-    }
-  }
-  d4 xo = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    const double av = sI[(16 * i + r16) * LS + 16 * i + 4 * r + k4];  // X_ii[m][4r + kk]
-    xo = __builtin_amdgcn_mfma_f64_16x16x4f64(av, s[r], xo, 0, 0, 0);
-  }
-#pragma unroll
-  for (int r = 0; r < 4; r++) sI[(16 * i + k4 + 4 * r) * LS + 16 * j + r16] = -xo[r];
 }
 
 // Panel elimination of columns P..P+15 by wave p (lane l = row l, a[] = row l of the panel),
@@ -164,9 +172,7 @@ __device__ __forceinline__ void panel_elim(double* sA, double* sx, int P, double
   double dn = readlane_d(a[0], P), c1 = readlane_d(a[0], P + 1);
   double r = __builtin_amdgcn_rcp(dn);
   r = __builtin_fma(r, __builtin_fma(-dn, r, 1.0), r);
-#ifndef MCS_LDLT_NEWTON1
   r = __builtin_fma(r, __builtin_fma(-dn, r, 1.0), r);
-#endif
 #pragma unroll
   for (int j = 0; j < 16; j++) {
     const int J = P + j;
@@ -184,13 +190,8 @@ __device__ __forceinline__ void panel_elim(double* sA, double* sx, int P, double
     if (j + 1 <= 13) {
       double* bn = sx + ((j + 1) & 1) * 64;
       bn[l] = a[j + 1];
-#ifdef MCS_LDLT_PIVOT_RL
-      dn = readlane_d(a[j + 1], J + 1);
-      c1n = readlane_d(a[j + 1], J + 2);
-#else
       dn = bn[J + 1];
       c1n = bn[J + 2];
-#endif
 #pragma unroll
       for (int m = j + 3; m < 16; m++) cn[m] = bn[P + m];
     } else {
@@ -212,7 +213,6 @@ __device__ __forceinline__ void panel_elim(double* sA, double* sx, int P, double
     rn = __builtin_fma(rn, e, rn);
     __builtin_amdgcn_sched_barrier(0);
     panel_bulk(a, cm, lj, j + 8, j + 9);
-#ifndef MCS_LDLT_NEWTON1
     __builtin_amdgcn_sched_barrier(0);
     e = __builtin_fma(-dn, rn, 1.0);
     __builtin_amdgcn_sched_barrier(0);
@@ -221,9 +221,6 @@ __device__ __forceinline__ void panel_elim(double* sA, double* sx, int P, double
     rn = __builtin_fma(rn, e, rn);
     __builtin_amdgcn_sched_barrier(0);
     panel_bulk(a, cm, lj, j + 10, 16);
-#else
-    panel_bulk(a, cm, lj, j + 9, 16);
-#endif
     r = rn;
     c1 = c1n;
   }
@@ -240,8 +237,8 @@ __device__ __forceinline__ void panel_elim(double* sA, double* sx, int P, double
   if (__any(diag && dsel == 0.0) && l == 0) *fail = 1;
 }
 
-// Partial sum of an off-diagonal block of L^-1: s += L_ik X_kj (one wave, MFMA), the k-th term
-// of S_ij = sum_{k=j}^{i-1} L_ik X_kj in offdiag_block's order (callers add k ascending).
+// Off-diagonal block of L^-1: X_ij = -X_ii S_ij with S_ij = sum_{k=j}^{i-1} L_ik X_kj, in two
+// parts.  xsum_add adds the k-th term, s += L_ik X_kj (one wave, MFMA; callers add k ascending).
 __device__ __forceinline__ void xsum_add(const double* sA, const double* sI, d4& s, int i, int k, int j) {
   const int l = threadIdx.x & 63, r16 = l & 15, k4 = l >> 4;
 #pragma unroll
@@ -251,7 +248,8 @@ __device__ __forceinline__ void xsum_add(const double* sA, const double* sI, d4&
     s = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, s, 0, 0, 0);
   }
 }
-// X_ij = -X_ii S_ij (one wave, MFMA), S in accumulator (= B-operand) layout, as offdiag_block
+// X_ij = -X_ii S_ij (one wave, MFMA); S stays in accumulator layout, which is the B-operand
+// layout of this product
 __device__ __forceinline__ void xfinish(double* sI, const d4& s, int i, int j) {
   const int l = threadIdx.x & 63, r16 = l & 15, k4 = l >> 4;
   d4 xo = {0.0, 0.0, 0.0, 0.0};
@@ -291,7 +289,8 @@ __device__ __forceinline__ void upd_block(double* sA, int p, int bi, int bj) {
 //   tail           : X_33, then X_3j = -X_33 S_3j.
 // Every block is updated by its panels in panel order and every S_ij accumulates k ascending
 // in one wave's registers, so the arithmetic is the same as a panel-at-a-time factorisation
-// followed by offdiag_block (same operations in the same order per element).  7 barriers.
+// followed by the L^-1 blocks one at a time (same operations in the same order per element).
+// 7 barriers.
 // On return sA holds L (strict lower) and D (diagonal), sI holds L^-1 (0 above the diagonal).
 __device__ __forceinline__ void factor_tile(double* sA, double* sI, int* fail) {
   const int t = threadIdx.x, l = t & 63, w = t >> 6;
@@ -388,105 +387,6 @@ __device__ __forceinline__ void factor_tile(double* sA, double* sI, int* fail) {
   __syncthreads();
   LDLT_STAMP(8);
 }
-
-#ifdef MCS_LDLT_FACTOR_V0
-// LDL^T of the 64x64 tile in sA (lower triangle read) and L^-1, blocked by 16-column panels.
-//   panel p (wave p, lane = row): columns 16p..16p+15 are eliminated in registers; the value of
-//     column j at another row comes from v_readlane (one wave: no barrier, no LDS).  The wave
-//     writes L (strict lower) and D (diagonal) of its columns into sA, and the unscaled columns
-//     C = L D of the rows below the panel, transposed, into the strict upper triangle (scratch:
-//     only the lower triangle and the diagonal of sA are results).
-//   trailing update: A[bi][bj] -= C_bi L_bj^T for the 16x16 blocks p < bj <= bi, on
-//     v_mfma_f64_16x16x4_f64, blocks spread over the 4 waves.
-//   L^-1: diagonal 16x16 blocks by forward substitution with lane = column (no cross-lane
-//     traffic; the L entries are LDS broadcasts), then block rows i = 1..3:
-//     X_ij = -X_ii (sum_{k=j}^{i-1} L_ik X_kj) on MFMA; the inner sum stays in accumulator
-//     layout, which is already the B-operand layout of the outer product.
-// The column-at-a-time version this replaces needed one barrier and a 64-row exchange per
-// column (~138k cycles per tile); here 8 barriers remain.
-// On return sA holds L (strict lower) and D (diagonal), sI holds L^-1 (0 above the diagonal).
-__device__ __forceinline__ void factor_tile_v0(double* sA, double* sI, int* fail) {
-  const int t = threadIdx.x, l = t & 63, w = t >> 6;
-  const int r16 = l & 15, k4 = l >> 4;
-  for (int p = 0; p < 4; p++) {
-    const int P = 16 * p;
-    if (w == p) {
-      double a[16];
-#pragma unroll
-      for (int c = 0; c < 16; c++) a[c] = sA[l * LS + P + c];
-#ifndef MCS_LDLT_FACTOR_STD
-      panel_elim(sA, sI + 62 * LS, P, a, fail);
-#else
-      // column broadcast through LDS (sI is scratch until the L^-1 phase): the wave writes its
-      // unscaled column once and reads the pivot and the panel rows back with uniform
-      // addresses (in-order LDS within one wave, no barrier); the pivot's reciprocal is one
-      // v_rcp_f64 + two Newton steps instead of a per-lane IEEE division
-      double* sc = sI + 63 * LS;   // row 63 of sI: written last (block row 3)
-#pragma unroll
-      for (int j = 0; j < 16; j++) {
-        const int J = P + j;
-        const double cj = a[j];
-        sc[l] = cj;
-        __builtin_amdgcn_wave_barrier();
-        double cm[16];
-#pragma unroll
-        for (int m = j; m < 16; m++) cm[m] = sc[P + m];
-        __builtin_amdgcn_wave_barrier();
-        const double dj = cm[j];
-        double r = __builtin_amdgcn_rcp(dj);
-        r = __builtin_fma(r, __builtin_fma(-dj, r, 1.0), r);
-        r = __builtin_fma(r, __builtin_fma(-dj, r, 1.0), r);
-        const double lj = cj * r;
-#pragma unroll
-        for (int m = j + 1; m < 16; m++) a[m] = __builtin_fma(-lj, cm[m], a[m]);
-        if (dj == 0.0 && l == 0) *fail = 1;
-        if (l >= J) sA[l * LS + J] = (l > J) ? lj : cj;
-        if (l >= P + 16) sA[J * LS + l] = cj;
-      }
-#endif
-    } else if (w == p - 1) {
-      // the previous panel's diagonal block is final: invert it while this panel runs
-      inv_diag16(sA, sI, 16 * (p - 1));
-    }
-    __syncthreads();
-    LDLT_STAMP(2 * p);
-    const int nb = 3 - p;
-    for (int b = w; b < nb * (nb + 1) / 2; b += 4) {
-      int q = 0, s = b;
-      while (s > q) { s -= q + 1; q++; }
-      const int bi = p + 1 + q, bj = p + 1 + s;
-      d4 acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int k0 = 0; k0 < 16; k0 += 4) {
-        const double av = sA[(P + k0 + k4) * LS + 16 * bi + r16];   // C[16 bi + m][P + k]
-        const double bv = sA[(16 * bj + r16) * LS + P + k0 + k4];   // L[16 bj + n][P + k]
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; r++) sA[(16 * bi + k4 + 4 * r) * LS + 16 * bj + r16] -= acc[r];
-    }
-    __syncthreads();
-    LDLT_STAMP(2 * p + 1);
-  }
-  // L^-1: diagonal blocks 0..2 were inverted during the next panel; block 3 now (wave 3),
-  // while wave 0 forms the off-diagonal block X_10 (it needs X_00, X_11 only) and the other
-  // waves clear the upper blocks
-  if (w == 3) inv_diag16(sA, sI, 48);
-  else if (w == 0) offdiag_block(sA, sI, 1, 0);
-  for (int e = t; e < TB * TB; e += 256) {
-    const int rr = e >> 6, cc = e & 63;
-    if ((cc >> 4) > (rr >> 4)) sI[rr * LS + cc] = 0.0;
-  }
-  __syncthreads();
-  LDLT_STAMP(8);
-  // remaining off-diagonal blocks, one block row at a time (row i needs the rows above it)
-  for (int i = 2; i < 4; i++) {
-    if (w < i) offdiag_block(sA, sI, i, w);
-    __syncthreads();
-  }
-}
-
-#endif
 
 // acc = X Y^T (64x64x64), wave w owns output columns [16w, 16w+16), acc[q] rows [16q, 16q+16)
 // v_mfma_f64_16x16x4_f64: lane l holds A[l&15][k=l>>4], B[k=l>>4][l&15];
@@ -723,10 +623,10 @@ __global__ __launch_bounds__(kBwdNT) void k_backward(const double* __restrict__ 
 // Hand-offs (MI355X_MICROARCH.md, visibility; cdna_hip_programming.md Guideline 16, R1):
 // payload stored write-through (sc1: 16-B buffer stores from LDS, 8-B stores from registers),
 // every storing wave drains vmcnt, a workgroup barrier, ONE lane stores the flag / counter
-// (relaxed, agent scope); the consumer's lane 0 polls relaxed with s_sleep, then ONE agent-scope
-// acquire + vmcnt drain before the workgroup barrier, then plain loads -- the MCS_PIPE_ACQUIRE
-// build; by default the consumers read with sc1 loads instead (kSc1Consume below).  Flag words
-// are zeroed by a memset on the stream before every launch.
+// (relaxed, agent scope); the consumer's lane 0 polls relaxed with s_sleep, the other waves join
+// it at a workgroup barrier, and the handed-off bytes are then read with sc1 loads (ld_h,
+// fetch_tile_h below), with no acquire.  Flag words are zeroed by a memset on the stream before
+// every launch.
 namespace {
 
 typedef __attribute__((address_space(1))) unsigned gu32;
@@ -762,23 +662,16 @@ __device__ __forceinline__ void store_tile_sc1(double* g, const double* s) {
 // sc1 flag store, the waiting lane polls that flag with sc1 loads and the other waves join it at
 // a barrier, one workgroup per CU (LDS), hipMalloc memory: MI355X_MICROARCH.md's hand-off table,
 // first row.  So the consumer reads the handed-off bytes with sc1 loads (16-B buffer loads for
-// tiles, 8-B global loads for words) and skips the agent acquire after each wait (an L2
-// invalidate on the diagonal chain twice per step).  Config E (n = 1194, 19 tile steps): solve
-// 0.395 -> 0.390 ms per trial, parity tests green on both forms (round 5,
+// tiles, 8-B global loads for words) and needs no agent acquire after a wait (an L2 invalidate
+// on the diagonal chain twice per step).  Measured against the form it replaced (one agent-scope
+// acquire + vmcnt drain after each wait, then plain loads), config E (n = 1194, 19 tile steps):
+// solve 0.395 -> 0.390 ms per trial, parity tests green on both forms (round 5,
 // profiles/r05_c_gba_host_ab.txt).
-// MCS_PIPE_ACQUIRE builds the acquire form.
-#ifdef MCS_PIPE_ACQUIRE
-constexpr bool kSc1Consume = false;
-#else
-constexpr bool kSc1Consume = true;
-#endif
 __device__ __forceinline__ double ld_h(const double* p) {
-  if (!kSc1Consume) return *p;
   return __longlong_as_double((long long)__hip_atomic_load((const gu64*)p, __ATOMIC_RELAXED,
                                                            __HIP_MEMORY_SCOPE_AGENT));
 }
 __device__ __forceinline__ void fetch_tile_h(d2 (&v)[8], const double* g) {
-  if (!kSc1Consume) { fetch_tile(v, g); return; }
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(g), 0, TB * TB * 8, 0x00020000);
 #pragma unroll
   for (int i = 0; i < 8; i++)
@@ -793,7 +686,7 @@ __device__ __forceinline__ void load_acc_h(double (&a)[4][4], const double* Aij)
     for (int r = 0; r < 4; r++) a[q][r] = ld_h(&Aij[(16 * q + k4 + 4 * r) * TB + col]);
 }
 
-// Lane 0 waits until *w_i >= v_i for every non-null word (bounded in time), then acquires; all threads get the
+// Lane 0 waits until *w_i >= v_i for every non-null word (bounded in time); all threads get the
 // outcome (false: timed out here or elsewhere).
 __device__ __forceinline__ bool wg_wait(const unsigned* w0, unsigned v0, const unsigned* w1, unsigned v1,
                                      const unsigned* w2, unsigned v2, unsigned* err, int* sh_ok,
@@ -806,10 +699,6 @@ __device__ __forceinline__ bool wg_wait(const unsigned* w0, unsigned v0, const u
       if (pl_load(err) != 0u) { ok = 0; break; }
       if (__builtin_amdgcn_s_memrealtime() - t0 > ticks) { pl_store(err, 1u); ok = 0; break; }
       __builtin_amdgcn_s_sleep(1);
-    }
-    if (ok && !kSc1Consume) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     *sh_ok = ok;
   }
@@ -849,38 +738,6 @@ __device__ __forceinline__ int tix(int I, int J, int T) { return (int)band_tiles
 // the first step whose product reaches tile row i (L_ik = 0 for k < i - (D - 1)); the product
 // counters count from there, so a tile's counter holds (products applied) = (next k) - kbase
 __device__ __forceinline__ int kbase(int i, int D) { return max(0, i - (D - 1)); }
-
-#ifdef MCS_LDLT_PROBE
-// probe builds only: diag step stamps [k][8] and task stamps [ticket][4] (s_memrealtime, 100 MHz)
-__device__ long long g_diag_stamps[128 * 8];
-__device__ long long g_task_stamps[65536 * 4];
-#define DSTAMP(k, i) do { if (threadIdx.x == 0 && (k) < 128) g_diag_stamps[(k) * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define TSTAMP(tk, i) do { if (threadIdx.x == 0 && (tk) < 65536) g_task_stamps[(tk) * 4 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define DSTAMP(k, i) do { } while (0)
-#define TSTAMP(tk, i) do { } while (0)
-#endif
-
-#ifdef MCS_PIPE_TRACE
-// debug builds only (tools/bench/pipe_debug.hip): events {wg, code, a, b} into host memory
-__device__ unsigned* g_pipe_trace;
-__device__ unsigned g_pipe_trace_n;
-__device__ __forceinline__ void ptrace(unsigned code, unsigned a, unsigned b) {
-  if (threadIdx.x == 0 && g_pipe_trace) {
-    const unsigned i = atomicAdd(&g_pipe_trace_n, 1u);
-    if (i < 65536) {
-      unsigned* e = g_pipe_trace + 4 * (size_t)i;
-      __hip_atomic_store(e + 1, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      __hip_atomic_store(e + 2, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      __hip_atomic_store(e + 3, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      __hip_atomic_store(e + 0, blockIdx.x + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
-}
-#define PTRACE(c, a, b) ptrace((c), (unsigned)(a), (unsigned)(b))
-#else
-#define PTRACE(c, a, b) do { } while (0)
-#endif
 
 // W = X Linv^T (registers, wave-row layout), then sX <- W D^-1 (= L), sY <- W, as k_panel does
 __device__ __forceinline__ void trsm_to_lds(double* sX, double* sY, const double* sI, const double* dvec) {
@@ -1194,7 +1051,7 @@ __global__ __launch_bounds__(256) void k_bwd(const double* __restrict__ L, const
         if (__builtin_amdgcn_s_memrealtime() - t0 > ticks) { pl_store(err, 1u); good = 0; break; }
         __builtin_amdgcn_s_sleep(1);
       }
-      if (good) {   // acquire x_i before the barrier, as wg_wait does
+      if (good) {   // acquire x_i before the barrier
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }

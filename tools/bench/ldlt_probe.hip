@@ -21,11 +21,7 @@ __global__ __launch_bounds__(256) void k_probe(const double* A, double* outL, do
   load_tile_lower(sK, A);
   __syncthreads();
   long long t1 = __builtin_amdgcn_s_memtime();
-#ifdef MCS_LDLT_FACTOR_V0
-  factor_tile_v0(sK, sI, &fail);
-#else
   factor_tile(sK, sI, &fail);
-#endif
   long long t2 = __builtin_amdgcn_s_memtime(), r2 = __builtin_amdgcn_s_memrealtime();
   for (int e = threadIdx.x; e < 4096; e += 256) {
     const int r = e >> 6, c = e & 63;

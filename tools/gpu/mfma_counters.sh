@@ -1,12 +1,12 @@
 # MFMA counters of the GlobalBA (config E) dense LDL^T: one rocprofv3 --pmc pass per counter
 # group on the bench's GlobalBA leg alone.  Usage: mfma_counters.sh TAG
 set -o pipefail
-cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
+cd "$(dirname "$0")/../.."; export TMPDIR=/tmp
 TAG=${1:-mf}
-O=gpurun_out/mf_$TAG; mkdir -p $O
+O=${MCS_OUT:-bench_out}/mf_$TAG; mkdir -p $O
 ARGS="--full --steps 1 --warmup 0 --multiframes 8 --no-cpu-baseline --ba-calls 0 --gba-calls 1 --d-multiframes 0 --bow-reps 0 --latency-reps 0"
-timeout -s KILL 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVES --output-format csv -d $O/a -o run -- python3 bench.py $ARGS > $O/bench_a.json 2> $O/a.err || { echo "pass a failed"; tail -5 $O/a.err; exit 1; }
-timeout -s KILL 300 rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_INSTS_VALU_MFMA_F64 --output-format csv -d $O/b -o run -- python3 bench.py $ARGS > $O/bench_b.json 2> $O/b.err || { echo "pass b failed"; tail -5 $O/b.err; exit 1; }
+timeout -k 10 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVES --output-format csv -d $O/a -o run -- python3 bench.py $ARGS > $O/bench_a.json 2> $O/a.err || { echo "pass a failed"; tail -5 $O/a.err; exit 1; }
+timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_INSTS_VALU_MFMA_F64 --output-format csv -d $O/b -o run -- python3 bench.py $ARGS > $O/bench_b.json 2> $O/b.err || { echo "pass b failed"; tail -5 $O/b.err; exit 1; }
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/t -o run -- python3 bench.py $ARGS > $O/bench_t.json 2> $O/t.err || { echo "trace failed"; tail -5 $O/t.err; exit 1; }
 A=$(find $O/a -name '*counter_collection.csv' | head -1)
 B=$(find $O/b -name '*counter_collection.csv' | head -1)

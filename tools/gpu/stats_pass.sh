@@ -1,9 +1,9 @@
-# The kernel-trace pass of final_profile.sh alone: TAG -> gpurun_out/fp_TAG/{kernel_stats.csv,
-# kernel_trace.csv, stage_kernel_trace.json, bench_stats.json}
+# The kernel-trace pass of final_profile.sh alone: TAG -> $MCS_OUT/fp_TAG/
+# {kernel_stats.csv, kernel_trace.csv, stage_kernel_trace.json, bench_stats.json} (default bench_out/)
 set -o pipefail
-cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out; export TMPDIR=/tmp
+cd "$(dirname "$0")/../.."; G=${MCS_OUT:-bench_out}; mkdir -p $G; export TMPDIR=/tmp
 TAG=${1:-r06}
-O=gpurun_out/fp_$TAG; mkdir -p $O
+O=$G/fp_$TAG; mkdir -p $O
 SARGS="--full --steps 5 --warmup 2 --split 1 --pipeline 0 --no-cpu-baseline --ba-calls 0 --gba-calls 0 --d-multiframes 0 --bow-reps 0 --latency-reps 0 --tri-reps 0"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- python3 bench.py $SARGS > $O/bench_stats.json 2> $O/stats.err || { echo "stats pass failed"; tail -5 $O/stats.err; exit 1; }
 S=$(find $O/stats -name '*kernel_stats.csv' | head -1); cp "$S" $O/kernel_stats.csv
