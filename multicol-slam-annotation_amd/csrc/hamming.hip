@@ -136,58 +136,75 @@ __global__ __launch_bounds__(kHamThreads) void k_top2(
 }
 
 // ---------------------------------------------------------------------------
-// 32-byte descriptors on the int8 matrix cores: with bits mapped to +-1 bytes,
-// dot(a, b) = 256 - 2 * Hamming(a, b), exactly (i32 accumulation of +-1 products).
-// v_mfma_i32_32x32x32_i8: A = 32 train rows, B = 32 query columns, K = 32 bits per
-// instruction, 8 instructions per 256-bit descriptor.  A workgroup (4 waves) owns 256
-// queries of one pair; each wave keeps the expanded bits of its 64 queries in registers
-// (B operands of both 32-column groups) and streams 64-train tiles, expanded once per
-// workgroup into LDS.  The accumulator puts one query column on each lane and 16 train rows
-// in its registers, so the running best/second-best keys (dist << 16 | train) are updated
+// 32-byte descriptors on the FP4 matrix cores: a descriptor bit becomes one FP4 e2m1 element,
+// +1.0 (nibble 0b0010) for a clear bit and -1.0 (0b1010) for a set one, and the query side is
+// complemented, so a bit position adds +1 where the two descriptors differ and -1 where they
+// agree: dot(train, ~query) = 2 Hamming - 256, exactly (small integers in f32).
+// v_mfma_scale_f32_32x32x64_f8f6f4: A = 32 train rows, B = 32 query columns, K = 64 bits per
+// instruction (32 per lane half, 4 VGPRs), 4 instructions per 256-bit descriptor.  Both
+// operands are built from a descriptor dword by the same rule (expand32_fp4), so whichever K
+// position the hardware gives a (lane half, register, nibble), the two sides agree on it.
+// A workgroup (4 waves) owns 256 queries of one pair; each wave keeps the expanded bits of its
+// 64 queries in registers (B operands of both 32-column groups) and streams 128-train tiles,
+// expanded once per workgroup into LDS.  The accumulator puts one query column on each lane
+// and 16 train rows in its registers, so the running best/second-best keys are updated
 // lane-locally; the two lane halves (different train rows) are merged at the end.
+//
+// KEYED form (every train index < 2^13): the matrix cores produce the top-2 key itself.  The
+// E8M0 block scales are 2^6 and 2^7, so a bit position weighs +-2^13 and the product sum is
+// 2^14 Hamming - 2^21; the accumulator starts at float(2^21 + 2^13 + the row's place in its
+// 32-train sub-tile), a loop constant, so the result is float(2^14 Hamming + 2^13 + place).
+// The running keys are kept relative to the sub-tile at hand: after each sub-tile they drop by
+// 32.0f (4 subtractions instead of 16 accumulator set-ups), so an earlier row's place is
+// negative and 2^13 + place stays in [0, 2^14) for every train index < 2^13: the keys order as
+// (Hamming, train index).  Every partial sum is an integer below 2^23, exact in f32, and
+// non-negative floats order like their bit patterns: min / med3 run on the raw bits, rows past
+// nt get kMfNone (a float so large that - 32.0f leaves it unchanged, sorting last), and only
+// the two winners become integers again.
+// Unkeyed form (nt > 8192): unit scales, C = 0, the key (dist << 16 | train) formed per distance.
 // ---------------------------------------------------------------------------
 typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
+typedef int v8i __attribute__((ext_vector_type(8)));
+typedef float v16f __attribute__((ext_vector_type(16)));
 
-// 4 bits -> 4 bytes of +1 (bit set) / -1 (bit clear)
-__device__ __forceinline__ uint32_t expand4(uint32_t nib) {
-  const uint32_t m = (nib * 0x00204081u) & 0x01010101u;
-  return ~(m * 0xFEu);
-}
-// 16 bits -> 16 bytes (element j <-> bit j)
-__device__ __forceinline__ v4i expand16(uint32_t bits) {
+// 32 bits -> 32 FP4 elements (4 dwords): nibble n of dword r <-> bit 4 n + r
+__device__ __forceinline__ v4i expand32_fp4(uint32_t bits) {
   v4i r;
-  r.x = (int)expand4(bits & 0xF);
-  r.y = (int)expand4((bits >> 4) & 0xF);
-  r.z = (int)expand4((bits >> 8) & 0xF);
-  r.w = (int)expand4((bits >> 12) & 0xF);
+  r.x = (int)(((bits << 3) & 0x88888888u) | 0x22222222u);
+  r.y = (int)(((bits << 2) & 0x88888888u) | 0x22222222u);
+  r.z = (int)(((bits << 1) & 0x88888888u) | 0x22222222u);
+  r.w = (int)((bits & 0x88888888u) | 0x22222222u);
+  return r;
+}
+constexpr int kKeyBits = 14;                 // keyed form: key = dist << 14 | (2^13 + relative train index)
+constexpr uint32_t kMfNone = 0x7F000000u;    // keyed form: no train (2^127 as a float)
+constexpr int kMfKeyedMax = 1 << 13;         // keyed form: at most this many trains
+
+constexpr int kMfTileT = 128;                 // trains per LDS tile
+constexpr int kMfSub = kMfTileT / 32;         // 32-train sub-tiles of a tile
+constexpr int kMfFetch = kMfTileT * 8 / 256;  // dwords of a tile per thread
+constexpr int kMfPitch = 128 + 16;            // expanded train row (bytes), padded against bank conflicts
+
+// float(bits) - 32.0f on the raw bits, as one plain v_add_f32 (the compiler otherwise pairs two
+// into v_pk_add_f32, which costs more than two adds beside MFMAs)
+__device__ __forceinline__ uint32_t sub32f(uint32_t k) {
+  uint32_t r;
+  asm("v_add_f32_e32 %0, 0xc2000000, %1" : "=v"(r) : "v"(k));
   return r;
 }
 
-// KEYED form (every train index < 2^13): the matrix cores produce the top-2 key up to the
-// train index.  Train bits map to -64 (set) / +64 (clear), query bits to +64 (set) / -64
-// (clear), so the product sum is -4096 (256 - 2 Hamming) = 2^13 Hamming - 2^20, and
-// key = sum + (2^20 + tile base) + the row's offset (one v_add3, the offset an inline constant)
-// = 2^13 Hamming + train index, ordered as (Hamming, train index) by min / med3 (< 2^22).
-__device__ __forceinline__ uint32_t expand4_64(uint32_t nib) {   // set -> 0xC0, clear -> 0x40
-  const uint32_t m = (nib * 0x00204081u) & 0x01010101u;
-  return (m << 7) | 0x40404040u;
+// one K = 64 step; the E8M0 scales (every byte of a scale dword the same) are 2^6 and 2^7 in
+// the keyed form, 2^0 otherwise
+template <bool KEYED>
+__device__ __forceinline__ v16f mfma_fp4(v4i a, v4i b, v16f c) {
+  constexpr int kScaleA = KEYED ? (int)0x85858585u : 0x7F7F7F7F;
+  constexpr int kScaleB = KEYED ? (int)0x86868686u : 0x7F7F7F7F;
+  const v8i a8 = {a.x, a.y, a.z, a.w, 0, 0, 0, 0}, b8 = {b.x, b.y, b.z, b.w, 0, 0, 0, 0};
+  return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, c, 4, 4, 0, kScaleA, 0, kScaleB);
 }
-__device__ __forceinline__ v4i expand16_64(uint32_t bits) {
-  v4i r;
-  r.x = (int)expand4_64(bits & 0xF);
-  r.y = (int)expand4_64((bits >> 4) & 0xF);
-  r.z = (int)expand4_64((bits >> 8) & 0xF);
-  r.w = (int)expand4_64((bits >> 12) & 0xF);
-  return r;
-}
-constexpr int kKeyBits = 13;
-
-constexpr int kMfTileT = 64;            // trains per LDS tile
-constexpr int kMfPitch = 256 + 16;      // expanded train row (bytes), padded against bank conflicts
 
 #ifndef MCS_TOP2_MINB
-#define MCS_TOP2_MINB 4   // 128 VGPRs, accumulators in VGPRs (no AGPR reads); measured 0.47 -> 0.44 ms
+#define MCS_TOP2_MINB 4   // 128 VGPRs, accumulators in VGPRs (no AGPR reads)
 #endif
 template <bool KEYED>
 __global__ __launch_bounds__(256, MCS_TOP2_MINB) void k_top2_mfma32(
@@ -214,26 +231,33 @@ __global__ __launch_bounds__(256, MCS_TOP2_MINB) void k_top2_mfma32(
   if (q_blk >= nq) return;   // uniform per block
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
   const int h = lane >> 5, col = lane & 31;
-  // ---- B operands: this wave's 64 queries (2 column groups x 8 k-steps)
-  v4i bq[2][8];
+  // ---- B operands: this wave's 64 queries (2 column groups x 4 k-steps), complemented; lane
+  // half h holds dword 2 s + h of k-step s
+  v4i bq[2][4];
 #pragma unroll
   for (int c = 0; c < 2; c++) {
     const int qi = q_blk + wv * 64 + c * 32 + col;
     const uint32_t* qd = reinterpret_cast<const uint32_t*>(Q + (int64_t)min(qi, max(nq - 1, 0)) * 32);
-    uint32_t w[8];
+    uint32_t w[4];
 #pragma unroll
-    for (int s = 0; s < 8; s++) w[s] = qd[s];
+    for (int s = 0; s < 4; s++) w[s] = qd[2 * s + h];
 #pragma unroll
-    for (int s = 0; s < 8; s++)   // KEYED: query set -> +64, i.e. the train map of ~bits
-      bq[c][s] = KEYED ? expand16_64(~(w[s] >> (16 * h)) & 0xFFFF) : expand16((w[s] >> (16 * h)) & 0xFFFF);
+    for (int s = 0; s < 4; s++) bq[c][s] = expand32_fp4(~w[s]);
   }
-  uint32_t k1[2] = {0xFFFFFFFFu, 0xFFFFFFFFu}, k2[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
+  constexpr uint32_t kNone = KEYED ? kMfNone : 0xFFFFFFFFu;
+  uint32_t k1[2] = {kNone, kNone}, k2[2] = {kNone, kNone};
+  // KEYED: what accumulator register r starts from, 2^21 + 2^13 + its row's place in a sub-tile
+  v16f cinit = {0};
+  if (KEYED) {
+#pragma unroll
+    for (int r = 0; r < 16; r++) cinit[r] = (float)((1 << 21) + (1 << 13) + 4 * h + (r & 3) + 8 * (r >> 2));
+  }
   // train tile bits, one tile ahead: the next tile's loads are in flight while this one is
-  // expanded and multiplied (each thread 2 dwords of 64 trains x 8 dwords)
-  uint32_t nb[2];
+  // expanded and multiplied (each thread kMfFetch dwords of 128 trains x 8 dwords)
+  uint32_t nb[kMfFetch];
   auto fetch = [&](int t0n) {
 #pragma unroll
-    for (int r = 0; r < 2; r++) {
+    for (int r = 0; r < kMfFetch; r++) {
       const int e = tid + 256 * r;
       const int tr = e >> 3, dw = e & 7;
       nb[r] = t0n + tr < nt ? reinterpret_cast<const uint32_t*>(T + (int64_t)(t0n + tr) * 32)[dw] : 0u;
@@ -242,76 +266,64 @@ __global__ __launch_bounds__(256, MCS_TOP2_MINB) void k_top2_mfma32(
   fetch(0);
   for (int t0 = 0; t0 < nt; t0 += kMfTileT) {
     const int ntile = min(kMfTileT, nt - t0);
-    const uint32_t cb[2] = {nb[0], nb[1]};
+    uint32_t cb[kMfFetch];
+#pragma unroll
+    for (int r = 0; r < kMfFetch; r++) cb[r] = nb[r];
     if (t0 + kMfTileT < nt) fetch(t0 + kMfTileT);
     __syncthreads();
-    // ---- expand the tile: 64 trains x 8 dwords; each thread 2 dwords -> 2 x 32 bytes
+    // ---- expand the tile: each dword -> 16 bytes at [train][dword]
 #pragma unroll
-    for (int r = 0; r < 2; r++) {
-      const int e = tid + 256 * r;          // 0..511
+    for (int r = 0; r < kMfFetch; r++) {
+      const int e = tid + 256 * r;
       const int tr = e >> 3, dw = e & 7;
-      const uint32_t bits = cb[r];
-      uint8_t* dst = s_t + tr * kMfPitch + dw * 32;
-      const v4i lo = KEYED ? expand16_64(bits & 0xFFFF) : expand16(bits & 0xFFFF);
-      const v4i hi = KEYED ? expand16_64(bits >> 16) : expand16(bits >> 16);
-      *reinterpret_cast<v4i*>(dst) = lo;
-      *reinterpret_cast<v4i*>(dst + 16) = hi;
+      *reinterpret_cast<v4i*>(s_t + tr * kMfPitch + dw * 16) = expand32_fp4(cb[r]);
     }
     __syncthreads();
-    // ---- two 32-train sub-tiles
+    // ---- the tile's 32-train sub-tiles
 #pragma unroll
-    for (int st = 0; st < 2; st++) {
+    for (int st = 0; st < kMfSub; st++) {
       if (st * 32 >= ntile) break;
       const int tb = t0 + st * 32 + 4 * h;
-      // KEYED: both accumulators start from the rows' key offsets (2^20 + tile base + the row's
-      // offset), one set shared by the two query groups, so the MFMA result is the key itself
-      v16i cinit = {0};
-      if (KEYED) {
-        const uint32_t tbk = (uint32_t)tb + (1u << 20);
-#pragma unroll
-        for (int r = 0; r < 16; r++) cinit[r] = (int)(tbk + (uint32_t)((r & 3) + 8 * (r >> 2)));
-      }
-      v16i acc0 = cinit, acc1 = cinit;
+      // KEYED: both accumulators start from the rows' key offsets, so the MFMA result is the key
+      v16f acc0 = cinit, acc1 = cinit;
       const uint8_t* arow = s_t + (st * 32 + col) * kMfPitch + 16 * h;
 #pragma unroll
-      for (int s = 0; s < 8; s++) {
+      for (int s = 0; s < 4; s++) {
         const v4i a = *reinterpret_cast<const v4i*>(arow + 32 * s);
-        acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bq[0][s], acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bq[1][s], acc1, 0, 0, 0);
+        acc0 = mfma_fp4<KEYED>(a, bq[0][s], acc0);
+        acc1 = mfma_fp4<KEYED>(a, bq[1][s], acc1);
       }
-      const bool full = st * 32 + 32 <= ntile;
-      if (KEYED) {
-        uint32_t key0[16], key1[16];
+      uint32_t key0[16], key1[16];
 #pragma unroll
-        for (int r = 0; r < 16; r++) {
-          key0[r] = (uint32_t)acc0[r];
-          key1[r] = (uint32_t)acc1[r];
+      for (int r = 0; r < 16; r++) {
+        if (KEYED) {
+          key0[r] = __float_as_uint(acc0[r]);
+          key1[r] = __float_as_uint(acc1[r]);
+        } else {   // acc = 2 Hamming - 256
+          const uint32_t trow = (uint32_t)(tb + (r & 3) + 8 * (r >> 2));
+          key0[r] = ((uint32_t)((int)acc0[r] + 256) >> 1 << 16) | trow;
+          key1[r] = ((uint32_t)((int)acc1[r] + 256) >> 1 << 16) | trow;
         }
-        if (!full) {   // the last, partial tile (a scalar branch: no selects in full tiles)
-          asm volatile("" ::: "memory");
+      }
+      if (st * 32 + 32 > ntile) {   // the last, partial tile (a scalar branch: no selects in full tiles)
+        asm volatile("" ::: "memory");
 #pragma unroll
-          for (int r = 0; r < 16; r++)
-            if (tb + (r & 3) + 8 * (r >> 2) >= nt) { key0[r] = 0xFFFFFFFFu; key1[r] = 0xFFFFFFFFu; }
-        }
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-          k2[0] = med3_u32(k1[0], key0[r], k2[0]);
-          k1[0] = min(k1[0], key0[r]);
-          k2[1] = med3_u32(k1[1], key1[r], k2[1]);
-          k1[1] = min(k1[1], key1[r]);
-        }
-        continue;
+        for (int r = 0; r < 16; r++)
+          if (tb + (r & 3) + 8 * (r >> 2) >= nt) { key0[r] = kNone; key1[r] = kNone; }
       }
 #pragma unroll
       for (int r = 0; r < 16; r++) {
-        const int trow = tb + (r & 3) + 8 * (r >> 2);
-        const uint32_t d0 = (uint32_t)(256 - acc0[r]) >> 1, d1 = (uint32_t)(256 - acc1[r]) >> 1;
-        uint32_t key0 = (d0 << 16) | (uint32_t)trow, key1 = (d1 << 16) | (uint32_t)trow;
-        if (!full && trow >= nt) { key0 = 0xFFFFFFFFu; key1 = 0xFFFFFFFFu; }
-        k2[0] = med3_u32(k1[0], key0, k2[0]);
-        k1[0] = min(k1[0], key0);
-        k2[1] = med3_u32(k1[1], key1, k2[1]);
-        k1[1] = min(k1[1], key1);
+        k2[0] = med3_u32(k1[0], key0[r], k2[0]);
+        k1[0] = min(k1[0], key0[r]);
+        k2[1] = med3_u32(k1[1], key1[r], k2[1]);
+        k1[1] = min(k1[1], key1[r]);
+      }
+      if (KEYED) {   // re-base the running keys to the next sub-tile
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+          k1[c] = sub32f(k1[c]);
+          k2[c] = sub32f(k2[c]);
+        }
       }
     }
   }
@@ -324,13 +336,18 @@ __global__ __launch_bounds__(256, MCS_TOP2_MINB) void k_top2_mfma32(
     const int qi = q_blk + wv * 64 + c * 32 + col;
     if (h == 0 && qi < nq) {
       const int64_t o = (int64_t)p * cap_out + qi;
-      const bool h1 = b1 != 0xFFFFFFFFu, h2 = b2 != 0xFFFFFFFFu;
+      const bool h1 = b1 != kNone, h2 = b2 != kNone;
+      // KEYED: the winners are floats holding the integer key, its index field 2^13 + the train
+      // index relative to the end of the last sub-tile
+      const uint32_t v1 = KEYED && h1 ? (uint32_t)__uint_as_float(b1) : b1;
+      const uint32_t v2 = KEYED && h2 ? (uint32_t)__uint_as_float(b2) : b2;
       constexpr int kIb = KEYED ? kKeyBits : 16;
       constexpr uint32_t kIm = (1u << kIb) - 1u;
-      best_idx[o] = h1 ? (int)(b1 & kIm) : -1;
-      best_dist[o] = h1 ? (int)(b1 >> kIb) : none;
-      second_idx[o] = h2 ? (int)(b2 & kIm) : -1;
-      second_dist[o] = h2 ? (int)(b2 >> kIb) : none;
+      const int ibase = KEYED ? ((nt + 31) & ~31) - (1 << 13) : 0;
+      best_idx[o] = h1 ? (int)(v1 & kIm) + ibase : -1;
+      best_dist[o] = h1 ? (int)(v1 >> kIb) : none;
+      second_idx[o] = h2 ? (int)(v2 & kIm) + ibase : -1;
+      second_dist[o] = h2 ? (int)(v2 >> kIb) : none;
     }
   }
 }
@@ -414,7 +431,7 @@ int mcs_hamming_top2_device(const uint8_t* d_q, int32_t nq, const uint8_t* d_t, 
   if (nq <= 0) return MCS_OK;
   if (nt > 65535) { set_error("top2: at most 65535 train descriptors"); return MCS_ERR_ARG; }
   if (bytes == 32) {
-    auto* kfn = nt <= (1 << kKeyBits) ? k_top2_mfma32<true> : k_top2_mfma32<false>;
+    auto* kfn = nt <= kMfKeyedMax ? k_top2_mfma32<true> : k_top2_mfma32<false>;
     hipLaunchKernelGGL(kfn, dim3((nq + 255) / 256, 1), dim3(256), 0, (hipStream_t)stream,
                        d_q, d_t, (const int32_t*)nullptr, (const int32_t*)nullptr, (int64_t)0, nq,
                        nt, nq, d_best_idx, d_best_dist, d_second_idx, d_second_dist);
@@ -439,7 +456,7 @@ int mcs_hamming_top2_batch_device(const uint8_t* d_desc, const int32_t* d_counts
   if (!d_desc || !d_counts || !d_pairs || cap <= 0) return MCS_ERR_ARG;
   if (cap > 65535) { set_error("top2: capacity above 65535"); return MCS_ERR_ARG; }
   if (bytes == 32) {   // a pair's train count is <= cap
-    auto* kfn = cap <= (1 << kKeyBits) ? k_top2_mfma32<true> : k_top2_mfma32<false>;
+    auto* kfn = cap <= kMfKeyedMax ? k_top2_mfma32<true> : k_top2_mfma32<false>;
     hipLaunchKernelGGL(kfn, dim3((cap + 255) / 256, n_pairs), dim3(256), 0,
                        (hipStream_t)stream, d_desc, d_desc, d_counts, d_pairs,
                        (int64_t)cap * bytes, 0, 0, cap, d_best_idx, d_best_dist, d_second_idx,
