@@ -17,10 +17,11 @@
 //   * cOptimizer::LocalBundleAdjustment rounds + culling (src/cOptimizer.cpp:771-903),
 //     BundleAdjustment (:73-261) and PoseOptimization (:264-486)
 //
-// PARITY STATUS: unpinned against the reference binary.  The MultiCol edge needs OpenCV
-// (absent); the vendored g2o core needs the cmake-generated ThirdParty/g2o/config.h
-// (core/openmp_mutex.h:30 includes "../../config.h"), so it is unbuildable here without a
-// stand-in header.  The restatement is checked by the properties in tests/test_ba.py.
+// PARITY STATUS: optimize() is pinned at tolerance against the reference's compiled g2o
+// (oracle/ref_g2o.mk + oracle/ref_g2o_driver.cpp -> tests/golden/g2o_optimize_ref.npz; DESIGN.md
+// section 4 holds the measured differences).  The MultiCol edge itself needs OpenCV (absent), so
+// that driver's edge calls oracle_ba_edge below: the one seam pinned only by mcsjacs1.npz and the
+// computeError text.
 // ============================================================================
 #include <algorithm>
 #include <cfloat>

@@ -25,6 +25,10 @@ Stand-ins (as gen_localba_ref.py):
     it is recorded as "no write" (the product's kf_slot / pt_slot = -1).
 
     python tests/golden/gen_globalba_ref.py [--ref /root/reference]
+
+--g2o: optimize() is run by the reference's own compiled g2o (see gen_localba_ref.py; the
+PoseOptimization scenarios on BlockSolverX + LinearSolverDense, as that function sets them up)
+-> globalba_g2o_ref.npz, without the inputs, which are globalba_ref.npz's.
 """
 import argparse
 import os
@@ -161,8 +165,7 @@ class GOptimizerG(L.GOptimizer):
         lvl = np.array([0 if e.level == self.level else 1 for e in E], np.uint8)
         before = self._flag()
         opts = ba.BAOptions(max_iterations=int(n), gain_threshold=ta.gain, terminate_max_iter=ta.maxit)
-        r = self.ob.ba_optimize(pr, opts, edge_level=lvl, stop_flag=int(before),
-                                points_fixed=bool(pfix and pfix.pop()))
+        r = self._round(pr, opts, lvl, before, mt, pts, points_fixed=bool(pfix and pfix.pop()))
         after = bool(r["stop_flag"])
         if self.force is not None:
             self.force[0] = after
@@ -534,7 +537,13 @@ def main():
     ap.add_argument("--ref", default="/root/reference")
     ap.add_argument("--out", default=os.path.join(HERE, "globalba_ref.npz"))
     ap.add_argument("--only", default=None)
+    ap.add_argument("--g2o", action="store_true",
+                    help="optimize() = the reference's compiled g2o (oracle/_ref) -> globalba_g2o_ref.npz")
     a = ap.parse_args()
+    if a.g2o:
+        L.USE_G2O[0] = True
+        if a.out == os.path.join(HERE, "globalba_ref.npz"):
+            a.out = os.path.join(HERE, "globalba_g2o_ref.npz")
     G, ob, n_stmt = load(a.ref)
     out = {"n_statements": n_stmt}
 
@@ -550,12 +559,18 @@ def main():
         if a.only and not re.fullmatch(a.only, name):
             continue
         run_gba(G, ob, name, kw, pose_only, stop, out)
+    L.SOLVER_DENSE[0] = True    # PoseOptimization's BlockSolverX over LinearSolverDense
     for name, *args in PO_SCENARIOS:
         if a.only and not re.fullmatch(a.only, name):
             continue
         run_po(G, name, args, out)
     out["gba_names"] = np.array([s[0] for s in GBA_SCENARIOS if not a.only or re.fullmatch(a.only, s[0])])
     out["po_names"] = np.array([s[0] for s in PO_SCENARIOS if not a.only or re.fullmatch(a.only, s[0])])
+    if a.g2o:   # the inputs are globalba_ref.npz's: only what the run produced is kept
+        po_in = ("key_mp", "key_cam", "key_pt", "key_oct", "pt_id", "pt_pos", "pose", "mc", "cam",
+                 "inv_sigma2")
+        out = {k: v for k, v in out.items()
+               if "_map_" not in k and not (k[0] == "p" and k.split("_", 1)[-1] in po_in)}
     np.savez_compressed(a.out, **out)
     print("wrote %s (%d statements translated)" % (a.out, n_stmt))
 

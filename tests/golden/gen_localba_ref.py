@@ -25,6 +25,11 @@ erased in each culling pass, the points that turned bad, the poses and points wr
 and each optimize() call (iterations, stop flag before / after).
 
     python tests/golden/gen_localba_ref.py [--ref /root/reference]
+
+--g2o: every optimize() is run by the reference's own compiled g2o instead (oracle/_ref/
+libg2o_ref.so through tests/ref_g2o_bind.py, one graph for all rounds, under the vertex ids the
+text assigned) -> localba_g2o_ref.npz, the small scenarios only and without the map inputs,
+which are localba_ref.npz's.
 """
 import argparse
 import math
@@ -273,12 +278,18 @@ class GTerminate(Standin):
         self.maxit = int(n)
 
 
+SOLVER_DENSE = [False]   # under --g2o: BlockSolverX + LinearSolverDense (PoseOptimization's)
+USE_G2O = [False]   # --g2o: optimize(n) runs the reference's compiled g2o (tests/ref_g2o_bind.py)
+
+
 class GOptimizer(Standin):
-    """g2o::SparseOptimizer: records the graph; optimize(n) = one restated g2o round."""
+    """g2o::SparseOptimizer: records the graph; optimize(n) = one restated g2o round, or under
+    --g2o one round of the reference's own SparseOptimizer on the same graph."""
 
     def __init__(self, ob, log):
         Standin.__init__(self)
         self.ob, self.log = ob, log
+        self._graph = None
         self.vertices, self.order, self.edges = {}, [], []
         self.force, self.aux, self.actions, self.level = None, None, [], None
 
@@ -317,6 +328,25 @@ class GOptimizer(Standin):
             return bool(self.force[0])
         return bool(self.aux)
 
+    def _round(self, pr, opts, lvl, before, mt, pts, points_fixed=False):
+        """One optimize(): the oracle's round, or (--g2o) the real one.  The real graph is built
+        once with the vertex ids the text assigned and serves every round, so the terminate
+        action and the flag it may install live as long as the text's optimizer does."""
+        if not USE_G2O[0]:
+            return self.ob.ba_optimize(pr, opts, edge_level=lvl, stop_flag=int(before),
+                                       points_fixed=points_fixed)
+        from tests import ref_g2o_bind as rg
+        if self._graph is None:
+            self._graph = rg.Graph(pr, opts, points_fixed=points_fixed,
+                                   has_stop_flag=self.force is not None,
+                                   pose_id=[v.id for v in mt], point_id=[v.id for v in pts],
+                                   dense_solver=SOLVER_DENSE[0])
+            assert self._graph.refused == 0
+        r = self._graph.round(opts.max_iterations, lvl, stop_flag=int(before))
+        if self.force is None:
+            r["stop_flag"] = r["report"].stop_flag
+        return r
+
     def m_optimize(self, n):
         from mcs_amd import ba
         ta = self.actions[0]
@@ -345,7 +375,7 @@ class GOptimizer(Standin):
         lvl = np.array([0 if e.level == self.level else 1 for e in E], np.uint8)
         before = self._flag()
         opts = ba.BAOptions(max_iterations=int(n), gain_threshold=ta.gain, terminate_max_iter=ta.maxit)
-        r = self.ob.ba_optimize(pr, opts, edge_level=lvl, stop_flag=int(before))
+        r = self._round(pr, opts, lvl, before, mt, pts)
         after = bool(r["stop_flag"])
         if self.force is not None:
             self.force[0] = after
@@ -488,7 +518,14 @@ def main():
     ap.add_argument("--out", default=os.path.join(HERE, "localba_ref.npz"))
     ap.add_argument("--dump", default=None)
     ap.add_argument("--big", action="store_true", help="the config-C-size case -> localba_ref_big.npz")
+    ap.add_argument("--g2o", action="store_true",
+                    help="optimize() = the reference's compiled g2o (oracle/_ref) -> localba_g2o_ref.npz")
     a = ap.parse_args()
+    if a.g2o:
+        assert not a.big, "--g2o keeps to the small scenarios"
+        USE_G2O[0] = True
+        if a.out == os.path.join(HERE, "localba_ref.npz"):
+            a.out = os.path.join(HERE, "localba_g2o_ref.npz")
     if a.big and a.out == os.path.join(HERE, "localba_ref.npz"):
         a.out = os.path.join(HERE, "localba_ref_big.npz")
     from tests import oracle_bind as ob
@@ -570,6 +607,8 @@ def main():
         out[p + "stop_after"] = -1 if cell is None else int(cell[0])
         print("%s: %d local KFs, %d edges, optimize log %s, %d points written" % (
             name, len(out[p + "local"]), len(out.get(p + "edges", [])), log, len(rec["point_write"])), flush=True)
+    if a.g2o:   # the inputs are localba_ref.npz's: only what the run produced is kept
+        out = {k: v for k, v in out.items() if "_map_" not in k}
     np.savez_compressed(a.out, **out)
     print("wrote %s (%d statements translated)" % (a.out, n_stmt))
 

@@ -10,7 +10,7 @@ called with pbStopFlag == NULL (src/cOptimizer.cpp:773-826).
 
 Tolerances as tests/test_ba.py: identical iteration counts, outlier sets and inlier counts;
 per-iteration robust chi2 rel 1e-6; pose abs 1e-8 (one 6x6 system per trial).
-Parity unpinned against a reference binary (g2o + OpenCV not buildable here).
+Against the reference's compiled g2o: tests/test_g2o_optimize_ref.py (cases P0, Pconv).
 """
 import numpy as np
 import pytest
