@@ -443,6 +443,98 @@ int mcs_fuse_select(int32_t rule, int32_t nq, int32_t n_cams, const int32_t* q_m
                     int32_t action_cap, int32_t* n_actions, int32_t* n_fused,
                     int32_t* requery_ids, int32_t* n_requery);
 
+/* ---- SearchBySim3: mutual projection matching under a loop Sim3 -----------------------------
+ *   int SearchBySim3(cMultiKeyFrame* pKF1, cMultiKeyFrame* pKF2, vector<cMapPoint*>& vpMatches12,
+ *                    const double& s12, const cv::Matx33d& R12, const cv::Vec3d& t12, double th)
+ *                                          src/cORBmatcher.cpp:1721-1988, called per loop candidate
+ *       by cLoopClosing::ComputeSim3 (src/cLoopClosing.cpp:369) with th = 10
+ * The whole function runs on the device, ONE current keyframe KF1 against a batch of T
+ * candidates KF2_t, each with its own Sim3: the transforms (GetPoseInverse,
+ * src/cMultiKeyFrame.cpp:152-157; invMat, src/cConverter.cpp:31-44; sR12, sR21, t21, :1741-1743),
+ * direction 1 (:1779-1872: every active map point of KF1 into KF2_t), direction 2 (:1874-1967:
+ * every active map point of KF2_t into KF1) and the agreement check (:1969-1987).  Nothing in it
+ * depends on map state that changes during the call, so there is no host tail.
+ *
+ * Per keypoint, as the text has it: only the keypoint's own camera c is searched
+ * (keypoint_to_cam, :1790, :1884); p3Dc = the Sim3 chain in the rig frame, p4Dc =
+ * invMat(M_c[c]) * (p3Dc, 1); the point is left when the RIG-frame z is negative (:1798, :1892:
+ * p3Dc2(2), not the camera-frame depth); WorldToImg (src/cam_model_omni.cpp:147-163) and
+ * isPointInMirrorMask(u, v, 0) (:165-180); dist3D = cv::norm of the camera-frame point in double
+ * against Get{Min,Max}DistanceInvariance (src/cMapPoint.cpp:498-508); level =
+ * min(lower_bound(scaleFactors, dist3D / minDistance), nLevels - 1), radius = th *
+ * scaleFactors[level]; GetFeaturesInArea(c, u, v, radius) (src/cMultiKeyFrame.cpp:703-746) in its
+ * enumeration order, octave level - 1 or level, DescriptorDistance64[Masked] between the MAP
+ * POINT's descriptor and the keypoint's row, first minimum under strict <, a match when bestDist
+ * <= th_high.  Direction 1 takes the camera model and M_c from KF2's rig; direction 2 takes the
+ * camera model from KF2's rig and M_c from KF1's (:1885, :1889).  Both keyframes share the rig in
+ * the reference; here n_cams, bytes, n_levels and the mirror size of the two sets must agree.
+ *
+ * Keyframes are mcs_fuse_targets sets: kf1 with n_targets == 1, kf2s with the T candidates.
+ * Unlike mcs_fuse_device, the device entry READS kp_cam (the keypoint's camera); rays is unused. */
+
+/* The map points in the keypoint slots of a packed keyframe set: slot i belongs to keypoint i of
+ * the set's packed arrays (n = the set's n_kp_total).  Rows of slots that are not active are not
+ * read. */
+typedef struct mcs_sim3_points {
+  int32_t n;
+  const double* pos;           /* [n][3] GetWorldPos */
+  const double* dist;          /* [n][2] mfMinDistance, mfMaxDistance (the 0.8 / 1.2 are applied) */
+  const uint8_t* desc;         /* [n][bytes] GetDescriptorPtr: the map point's descriptor, not the keypoint's row */
+  const uint8_t* mask;         /* nullable [n][bytes]; given iff the keyframes have masks */
+} mcs_sim3_points;
+
+/* Device scratch of mcs_search_by_sim3_device for batches of <= max_targets candidates of
+ * <= max_kp keypoints each (and a KF1 of <= max_kp): the transforms, and vnMatch1 / vnMatch2
+ * when the caller does not ask for them. */
+typedef struct mcs_sim3_workspace mcs_sim3_workspace;
+int mcs_sim3_workspace_create(int32_t device, int32_t max_targets, int32_t max_kp,
+                              mcs_sim3_workspace** out);
+void mcs_sim3_workspace_destroy(mcs_sim3_workspace* ws);
+
+/* SearchBySim3 (src/cORBmatcher.cpp:1721-1988) for all candidates in three launches.  Every
+ * pointer inside the sets / points and every d_* is a device pointer.  n1 = kf1->n_kp_total.
+ *   d_active1 [T][n1]           the caller's snapshot of pMP && !vbAlreadyMatched1 && !pMP->isBad()
+ *                               (:1784-1788) per candidate, as vpMatches12 differs per candidate
+ *   d_active2 [n_kp_total of kf2s]  the same for :1878-1882, packed like the candidates
+ *   d_s12 [T], d_R12 [T][9] row-major, d_t12 [T][3]
+ *   th = the radius factor (10 at the call site), th_high = TH_HIGH_ of the cORBmatcher ctor
+ *   (:46-65): 3 * bytes, or floor(1.5 * bytes) with masks
+ * Out, indices local to their keyframe:
+ *   d_match1 [T][n1]            vnMatch1 (nullable: kept in the workspace)
+ *   d_match2 [n_kp_total]       vnMatch2, packed like the candidates (nullable likewise)
+ *   d_matches12 [T][n1]         idx2 when vnMatch1[i1] = idx2 >= 0 and vnMatch2[idx2] == i1, else -1
+ *                               (vpMatches12[i1] = vpMapPoints2[idx2], :1981)
+ *   d_n_found [T]               the return value per candidate
+ * A direction-1 hit on a KF2 keypoint that is not active gives no match: its vnMatch2 is -1.
+ * Stream-ordered, no host synchronisation, no allocation with a workspace; ws NULL = a temporary
+ * one is allocated and freed (which synchronises).  Offsets, counts, cell entries and camera
+ * indices are device data and are clamped in the kernel: a malformed set reads nothing outside
+ * its buffers, and a keypoint whose camera is outside [0, n_cams) never matches.
+ * MCS_ERR_ARG: bytes not 16 / 32 / 64, more than 8 cameras, masks on one side only,
+ * kf1->n_targets != 1, T or the keypoint counts above the workspace, a keyframe of 2^19
+ * keypoints or more (kf1 here; per candidate it is the caller's precondition, as in
+ * mcs_fuse_device), a null buffer, n_cams / bytes / n_levels / mirror size differing between kf1
+ * and kf2s. */
+int mcs_search_by_sim3_device(mcs_sim3_workspace* ws, const mcs_fuse_targets* kf1,
+                              const mcs_sim3_points* pts1, const mcs_fuse_targets* kf2s,
+                              const mcs_sim3_points* pts2, const uint8_t* d_active1,
+                              const uint8_t* d_active2, const double* d_s12, const double* d_R12,
+                              const double* d_t12, double th, int32_t th_high, int32_t* d_match1,
+                              int32_t* d_match2, int32_t* d_matches12, int32_t* d_n_found,
+                              void* stream);
+
+/* Host-buffer form for the call site (src/cLoopClosing.cpp:369): builds every grid
+ * (mcs_frame_grid_build; cell_ptr / cell_kp of the sets are ignored), uploads, runs
+ * mcs_search_by_sim3_device on `device` and downloads; match1 / match2 nullable.  Also
+ * MCS_ERR_ARG for malformed offsets, a candidate of 2^19 keypoints or more and a kp_cam outside
+ * [0, n_cams); all argument errors are returned before any device use.  MCS_ERR_NO_DEVICE
+ * without a GPU. */
+int mcs_search_by_sim3(int32_t device, const mcs_fuse_targets* kf1, const mcs_sim3_points* pts1,
+                       const mcs_fuse_targets* kf2s, const mcs_sim3_points* pts2,
+                       const uint8_t* active1, const uint8_t* active2, const double* s12,
+                       const double* R12, const double* t12, double th, int32_t th_high,
+                       int32_t* match1, int32_t* match2, int32_t* matches12, int32_t* n_found);
+
 #ifdef __cplusplus
 }
 #endif

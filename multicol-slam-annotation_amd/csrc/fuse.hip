@@ -24,7 +24,6 @@ namespace mcs {
 namespace fuse {
 
 constexpr int kWPB = 4;            // waves per 256-thread workgroup, one (t, i, c) each
-constexpr int kPosBits = 20;       // key = dist << 20 | position in the window's enumeration
 constexpr int kMaxCams = 8;
 constexpr int kMaxKpPerTarget = 1 << 19;
 constexpr double kEpiThresh = 1e-2;   // :1398
@@ -123,10 +122,9 @@ __device__ __forceinline__ bool project(const Args& a, int t, int i, int c, doub
 }
 
 // One wave per (t, i, c).  Every lane computes the front half (it is wave-uniform); the window is
-// walked as k_window does: cells 64 at a time in ix-major order, a wave prefix sum over the cell
-// sizes flattens their keypoints.  A candidate passing |dx| <= r && |dy| <= r and the level test
-// gets the key dist << 20 | position-in-enumeration; the wave minimum is the reference's first
-// minimum under strict <.  Offsets, cell ranges and cell entries are clamped to the target.
+// walked by win::walk_best (proj_window.hpp), whose wave minimum is the reference's first minimum
+// under strict <; use_dist = 0 is rule 1 as written, which never assigns dist (:1507-1514).
+// Offsets, cell ranges and cell entries are clamped to the target.
 __global__ __launch_bounds__(256) void k_fuse(Args a) {
   const int lane = threadIdx.x & 63;
   const int64_t w = (int64_t)blockIdx.x * kWPB + (threadIdx.x >> 6);
@@ -148,52 +146,9 @@ __global__ __launch_bounds__(256) void k_fuse(Args a) {
     const int32_t* ckp = a.cell_kp + o;
     const uint8_t* qd = a.q_desc + (int64_t)i * a.bytes;
     const uint8_t* qm = a.q_mask ? a.q_mask + (int64_t)i * a.bytes : nullptr;
-    uint32_t best = 0xFFFFFFFFu;
-    int bestk = -1, pos = 0;
-    const int ncy = y1 - y0 + 1, ncell = (x1 - x0 + 1) * ncy;
-    for (int cb = 0; cb < ncell; cb += 64) {
-      const int ci = cb + lane;
-      int start = 0, len = 0;
-      if (ci < ncell) {
-        const int cell = (c * win::kCols + x0 + ci / ncy) * win::kRows + y0 + ci % ncy;
-        start = min(max(cptr[cell], 0), n_t);
-        len = min(max(cptr[cell + 1] - start, 0), n_t - start);
-      }
-      const int incl = dev::wave_incl_scan(len);
-      const int off = incl - len;
-      const int tot = __shfl(incl, 63);
-      for (int e0 = 0; e0 < tot; e0 += 64) {
-        const int e = e0 + lane;
-        int ow = 0;   // owning cell = the last lane whose offset is <= e
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1)
-          if (__shfl(off, ow + s) <= e) ow += s;
-        const int so = __shfl(start, ow), oo = __shfl(off, ow);
-        if (e < tot) {
-          const int k = ckp[so + (e - oo)];
-          if (k >= 0 && k < n_t) {
-            const int64_t g = (int64_t)o + k;
-            const int oc = a.kp_oct[g];
-            const double dx = (double)a.kp_xy[2 * g] - u, dy = (double)a.kp_xy[2 * g + 1] - v;
-            if (fabs(dx) <= r && fabs(dy) <= r && !(oc < lv - 1 || oc > lv)) {
-              const int dist = a.use_dist ? win::ham(qd, a.desc + g * a.bytes, qm,
-                                                     a.mask ? a.mask + g * a.bytes : nullptr, a.bytes)
-                                          : 0;   // rule 1 as written never assigns dist (:1507-1514)
-              const uint32_t key = ((uint32_t)dist << kPosBits) | ((uint32_t)(pos + e) & ((1u << kPosBits) - 1));
-              if (key < best) { best = key; bestk = k; }
-            }
-          }
-        }
-      }
-      pos += tot;
-    }
-    uint32_t mn = best;
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) mn = min(mn, (uint32_t)__shfl_xor((int)mn, s, 64));
-    if (mn != 0xFFFFFFFFu) {
-      const int src = __ffsll((unsigned long long)__ballot(best == mn)) - 1;
-      const int k = __shfl(bestk, src);
-      bd = (int)(mn >> kPosBits);
+    int k = -1;
+    if (win::walk_best(lane, c, x0, x1, y0, y1, cptr, ckp, o, n_t, a.kp_xy, a.kp_oct, a.desc, a.mask,
+                       a.bytes, qd, qm, u, v, r, lv, a.use_dist, &bd, &k)) {
       if (bd <= a.th_low) {
         bk = k;
         if (a.rule == 0 && a.epi_ok)

@@ -1,7 +1,8 @@
-// Device functions shared by frame.hip, window.hip, hamming.hip and fuse.hip: the omni
-// projection (cayley2rot, M_t M_c, WorldToCamHom_fast / WorldToImg, ImgToWorld), the window cell
-// range of GetFeaturesInArea, the descriptor distance of a window candidate and
-// CheckDistEpipolarLine.  One definition each, so every entry that uses them gives the same bits.
+// Device functions shared by frame.hip, window.hip, hamming.hip, fuse.hip and sim3_match.hip: the
+// omni projection (cayley2rot, M_t M_c, WorldToCamHom_fast / WorldToImg, ImgToWorld), the window
+// cell range of GetFeaturesInArea, the descriptor distance of a window candidate, the
+// wave-per-query window walk and CheckDistEpipolarLine.  One definition each, so every entry that
+// uses them gives the same bits.
 // Translation units that include this are compiled with -ffp-contract=off; double ops are spelled
 // with _rn intrinsics where an FMA could otherwise be formed.
 #pragma once
@@ -81,6 +82,18 @@ __device__ inline void mtmc44(const double* Mt, const double* Mc, double* R, dou
     }
 }
 
+// WorldToImg (cam_model_omni.cpp:147-163); cam = c d e u0 v0 invP[12]
+__device__ __forceinline__ void world_to_img(const double* cam, double x, double y, double z,
+                                             double& u, double& v) {
+  double norm = __dsqrt_rn(__dadd_rn(__dmul_rn(x, x), __dmul_rn(y, y)));
+  if (norm == 0.0) norm = 1e-14;
+  const double theta = atan(__ddiv_rn(-z, norm));
+  const double rho = horner_n(cam + 5, 12, theta);
+  const double uu = __dmul_rn(__ddiv_rn(x, norm), rho), vv = __dmul_rn(__ddiv_rn(y, norm), rho);
+  u = __dadd_rn(__dadd_rn(__dmul_rn(uu, cam[0]), __dmul_rn(vv, cam[1])), cam[3]);
+  v = __dadd_rn(__dadd_rn(__dmul_rn(uu, cam[2]), vv), cam[4]);
+}
+
 // WorldToCamHom_fast (cam_system_omni.cpp:92-112): invMat(M_t M_c) * [X 1], then WorldToImg
 __device__ inline void world_to_cam_img(const double* R, const double* t, const double* cam,
                                         const double* X, double& u, double& v) {
@@ -99,14 +112,7 @@ __device__ inline void world_to_cam_img(const double* R, const double* t, const 
     s = __dadd_rn(s, __dmul_rn(ti[i], 1.0));
     Xc[i] = s;
   }
-  const double x = Xc[0], y = Xc[1], z = Xc[2];   // WorldToImg (cam_model_omni.cpp:147-163)
-  double norm = __dsqrt_rn(__dadd_rn(__dmul_rn(x, x), __dmul_rn(y, y)));
-  if (norm == 0.0) norm = 1e-14;
-  const double theta = atan(__ddiv_rn(-z, norm));
-  const double rho = horner_n(cam + 5, 12, theta);
-  const double uu = __dmul_rn(__ddiv_rn(x, norm), rho), vv = __dmul_rn(__ddiv_rn(y, norm), rho);
-  u = __dadd_rn(__dadd_rn(__dmul_rn(uu, cam[0]), __dmul_rn(vv, cam[1])), cam[3]);
-  v = __dadd_rn(__dadd_rn(__dmul_rn(uu, cam[2]), vv), cam[4]);
+  world_to_img(cam, Xc[0], Xc[1], Xc[2], u, v);
 }
 
 }  // namespace frm
@@ -155,6 +161,71 @@ __device__ __forceinline__ int ham(const uint8_t* q, const uint8_t* t, const uin
     d += __popc(x & ma[w]) + __popc(x & mb[w]);
   }
   return d / 2;
+}
+
+// The window walk of the wave-per-query searches (k_fuse, k_sim3_search), after cell_range said
+// the window is not empty.  The whole wave calls it with wave-uniform arguments.  Cells are taken
+// 64 at a time in ix-major order (GetFeaturesInArea's enumeration, cMultiKeyFrame.cpp:731-743), a
+// wave prefix sum over the cell sizes flattens their keypoints.  A candidate passing
+// |dx| <= r && |dy| <= r and the level test (octave lv - 1 or lv) gets the key
+// dist << kPosBits | position-in-enumeration; the wave minimum is the reference's first minimum
+// under strict <.  o = the keyframe's first keypoint in the packed arrays, n_t = its (clamped)
+// count, cptr = its cell_ptr row, ckp = its cell_kp list; cell ranges and entries are clamped to
+// n_t.  use_dist = 0: every candidate counts as distance 0.  false = no candidate passed.
+constexpr int kPosBits = 20;       // key = dist << 20 | position in the window's enumeration
+
+__device__ __forceinline__ bool walk_best(int lane, int c, int x0, int x1, int y0, int y1,
+                                          const int32_t* cptr, const int32_t* ckp, int64_t o, int n_t,
+                                          const float* kp_xy, const int32_t* kp_oct,
+                                          const uint8_t* desc, const uint8_t* mask, int bytes,
+                                          const uint8_t* qd, const uint8_t* qm, double u, double v,
+                                          double r, int lv, int use_dist, int* out_dist, int* out_k) {
+  uint32_t best = 0xFFFFFFFFu;
+  int bestk = -1, pos = 0;
+  const int ncy = y1 - y0 + 1, ncell = (x1 - x0 + 1) * ncy;
+  for (int cb = 0; cb < ncell; cb += 64) {
+    const int ci = cb + lane;
+    int start = 0, len = 0;
+    if (ci < ncell) {
+      const int cell = (c * kCols + x0 + ci / ncy) * kRows + y0 + ci % ncy;
+      start = min(max(cptr[cell], 0), n_t);
+      len = min(max(cptr[cell + 1] - start, 0), n_t - start);
+    }
+    const int incl = dev::wave_incl_scan(len);
+    const int off = incl - len;
+    const int tot = __shfl(incl, 63);
+    for (int e0 = 0; e0 < tot; e0 += 64) {
+      const int e = e0 + lane;
+      int ow = 0;   // owning cell = the last lane whose offset is <= e
+#pragma unroll
+      for (int s = 32; s > 0; s >>= 1)
+        if (__shfl(off, ow + s) <= e) ow += s;
+      const int so = __shfl(start, ow), oo = __shfl(off, ow);
+      if (e < tot) {
+        const int k = ckp[so + (e - oo)];
+        if (k >= 0 && k < n_t) {
+          const int64_t g = o + k;
+          const int oc = kp_oct[g];
+          const double dx = (double)kp_xy[2 * g] - u, dy = (double)kp_xy[2 * g + 1] - v;
+          if (fabs(dx) <= r && fabs(dy) <= r && !(oc < lv - 1 || oc > lv)) {
+            const int dist = use_dist ? ham(qd, desc + g * bytes, qm, mask ? mask + g * bytes : nullptr, bytes)
+                                      : 0;
+            const uint32_t key = ((uint32_t)dist << kPosBits) | ((uint32_t)(pos + e) & ((1u << kPosBits) - 1));
+            if (key < best) { best = key; bestk = k; }
+          }
+        }
+      }
+    }
+    pos += tot;
+  }
+  uint32_t mn = best;
+#pragma unroll
+  for (int s = 32; s > 0; s >>= 1) mn = min(mn, (uint32_t)__shfl_xor((int)mn, s, 64));
+  if (mn == 0xFFFFFFFFu) return false;
+  const int src = __ffsll((unsigned long long)__ballot(best == mn)) - 1;
+  *out_k = __shfl(bestk, src);
+  *out_dist = (int)(mn >> kPosBits);
+  return true;
 }
 
 }  // namespace win

@@ -511,4 +511,101 @@ inline std::vector<int> Fuse(int rule, const FuseRig& rig, const std::vector<con
   return n_fused;
 }
 
+// cORBmatcher::SearchBySim3 (src/cORBmatcher.cpp:1721-1988) at cLoopClosing::ComputeSim3
+// (src/cLoopClosing.cpp:369): the current keyframe against every loop candidate whose RANSAC has
+// returned a Sim3, in one device call (mcs_search_by_sim3).  There is no host tail.
+struct Sim3KeyFrame {               // a keyframe and the map points in its keypoint slots
+  const FuseKeyFrame* kf = nullptr;
+  std::vector<uint8_t> has_mp, bad; // [n] GetMapPointMatches()[i] != NULL, ->isBad()
+  std::vector<double> pos, dist;    // [n][3] GetWorldPos, [n][2] mfMinDistance mfMaxDistance
+  std::vector<uint8_t> desc, mask;  // [n][bytes] GetDescriptorPtr / GetDescriptorMaskPtr (the point's, not the row's)
+};
+struct Sim3Candidate {
+  Sim3KeyFrame kf2;
+  double s12 = 1.0, R12[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t12[3] = {0, 0, 0};
+  std::vector<int32_t> matches12;   // in / out [n1]: vpMatches12 as a keypoint of kf2 (its map point), -1 = NULL
+  // [n1] (int)vpMatches12[i]->GetIndexInKeyFrame(pKF2)[0]: the FIRST keypoint of kf2 the point
+  // observes, -1 when it observes none (src/cMapPoint.cpp:436-445); read where matches12[i] >= 0
+  std::vector<int32_t> first_idx_in_kf2;
+};
+
+// vbAlreadyMatched1 / 2 exactly as :1758-1774 build them (only the first index of a matched
+// point, and only when it lies in [0, N2)), then the conditions under which the two loops take a
+// slot (:1784-1788, :1878-1882): a point, not already matched, not bad.
+inline void Sim3Flags(const Sim3KeyFrame& kf1, const Sim3Candidate& c, std::vector<uint8_t>& already1,
+                      std::vector<uint8_t>& already2, std::vector<uint8_t>& active1,
+                      std::vector<uint8_t>& active2) {
+  const int N1 = (int)kf1.has_mp.size(), N2 = (int)c.kf2.has_mp.size();
+  if ((int)c.matches12.size() != N1 || (int)c.first_idx_in_kf2.size() != N1 || (int)kf1.bad.size() != N1 ||
+      (int)c.kf2.bad.size() != N2)
+    throw std::invalid_argument("SearchBySim3: matches12 / first_idx_in_kf2 / bad do not fit the keyframes");
+  already1.assign(N1, 0); already2.assign(N2, 0);
+  for (int i = 0; i < N1; i++) {
+    if (c.matches12[i] < 0) continue;
+    already1[i] = 1;
+    const int idx2 = c.first_idx_in_kf2[i];
+    if (idx2 >= 0 && idx2 < N2) already2[idx2] = 1;
+  }
+  active1.assign(N1, 0); active2.assign(N2, 0);
+  for (int i = 0; i < N1; i++) active1[i] = kf1.has_mp[i] && !already1[i] && !kf1.bad[i];
+  for (int i = 0; i < N2; i++) active2[i] = c.kf2.has_mp[i] && !already2[i] && !c.kf2.bad[i];
+}
+
+// Returns nFound per candidate and writes the new matches into each candidate's matches12
+// (vpMatches12[i1] = vpMapPoints2[idx2], :1981).  th = 10 at the call site; th_high = the matcher's
+// TH_HIGH_ (3 * bytes, or floor(1.5 * bytes) with masks).
+inline std::vector<int> SearchBySim3(const FuseRig& rig, const Sim3KeyFrame& kf1, std::vector<Sim3Candidate>& cands,
+                                     int bytes, double th, int th_high, int device = 0) {
+  const int T = (int)cands.size(), C = rig.n_cams;
+  if (T == 0) return {};
+  if (!kf1.kf) throw std::invalid_argument("SearchBySim3: kf1 has no keyframe");
+  const int n1 = (int)kf1.kf->kp_octave.size();
+  const bool masked = !kf1.kf->mask.empty();
+  std::vector<int32_t> off(1, 0), oct, cam;
+  std::vector<float> xy;
+  std::vector<uint8_t> desc, mask, pdesc, pmask, act1, act2, a1, a2, am1, am2;
+  std::vector<double> m_t, pos, dist, s12, R12, t12;
+  for (Sim3Candidate& c : cands) {
+    if (!c.kf2.kf) throw std::invalid_argument("SearchBySim3: a candidate has no keyframe");
+    const FuseKeyFrame& k = *c.kf2.kf;
+    if (masked != !k.mask.empty() || masked != !c.kf2.mask.empty() || masked != !kf1.mask.empty())
+      throw std::invalid_argument("SearchBySim3: masks for every keyframe and every point or none");
+    Sim3Flags(kf1, c, am1, am2, a1, a2);
+    act1.insert(act1.end(), a1.begin(), a1.end());
+    act2.insert(act2.end(), a2.begin(), a2.end());
+    off.push_back(off.back() + (int32_t)k.kp_octave.size());
+    xy.insert(xy.end(), k.kp_xy.begin(), k.kp_xy.end());
+    oct.insert(oct.end(), k.kp_octave.begin(), k.kp_octave.end());
+    cam.insert(cam.end(), k.kp_cam.begin(), k.kp_cam.end());
+    desc.insert(desc.end(), k.desc.begin(), k.desc.end());
+    mask.insert(mask.end(), k.mask.begin(), k.mask.end());
+    m_t.insert(m_t.end(), k.m_t, k.m_t + 16);
+    pos.insert(pos.end(), c.kf2.pos.begin(), c.kf2.pos.end());
+    dist.insert(dist.end(), c.kf2.dist.begin(), c.kf2.dist.end());
+    pdesc.insert(pdesc.end(), c.kf2.desc.begin(), c.kf2.desc.end());
+    pmask.insert(pmask.end(), c.kf2.mask.begin(), c.kf2.mask.end());
+    s12.push_back(c.s12);
+    R12.insert(R12.end(), c.R12, c.R12 + 9);
+    t12.insert(t12.end(), c.t12, c.t12 + 3);
+  }
+  const int32_t L = (int32_t)rig.scale.size(), one[2] = {0, n1};
+  const FuseKeyFrame& k1 = *kf1.kf;
+  mcs_fuse_targets s1{1, n1, C, bytes, L, rig.mirror_w, rig.mirror_h, one, k1.kp_xy.data(), k1.kp_octave.data(),
+                      k1.kp_cam.data(), k1.desc.data(), masked ? k1.mask.data() : nullptr, nullptr, k1.m_t,
+                      rig.m_c.data(), rig.cam.data(), rig.mirror.data(), rig.grid_params.data(), rig.scale.data(),
+                      nullptr, nullptr};
+  mcs_fuse_targets s2{T, off.back(), C, bytes, L, rig.mirror_w, rig.mirror_h, off.data(), xy.data(), oct.data(),
+                      cam.data(), desc.data(), masked ? mask.data() : nullptr, nullptr, m_t.data(), rig.m_c.data(),
+                      rig.cam.data(), rig.mirror.data(), rig.grid_params.data(), rig.scale.data(), nullptr, nullptr};
+  mcs_sim3_points p1{n1, kf1.pos.data(), kf1.dist.data(), kf1.desc.data(), masked ? kf1.mask.data() : nullptr};
+  mcs_sim3_points p2{off.back(), pos.data(), dist.data(), pdesc.data(), masked ? pmask.data() : nullptr};
+  std::vector<int32_t> m12((size_t)T * n1 + 1), nf(T + 1);
+  check(mcs_search_by_sim3(device, &s1, &p1, &s2, &p2, act1.data(), act2.data(), s12.data(), R12.data(), t12.data(), th,
+                           th_high, nullptr, nullptr, m12.data(), nf.data()), "mcs_search_by_sim3");
+  for (int t = 0; t < T; t++)
+    for (int i = 0; i < n1; i++)
+      if (m12[(size_t)t * n1 + i] >= 0) cands[t].matches12[i] = m12[(size_t)t * n1 + i];
+  return std::vector<int>(nf.begin(), nf.begin() + T);
+}
+
 }  // namespace mcs

@@ -169,6 +169,13 @@ SIGNATURES = {
     "mcs_fuse": (ctypes.c_int, [_I32, _I32, _I32, _P, _P, ctypes.c_double, _I32, _P, _P, _P, _P]),
     "mcs_fuse_select": (ctypes.c_int, [_I32, _I32, _I32, _P, _P, _P, _I32, _P, _P, _I32, _P, _P, _I32,
                                        _P, _P, _P, _P]),
+    # SearchBySim3 (include/mcs_matcher.h; wrappers in mcs_amd/sim3_match.py)
+    "mcs_sim3_workspace_create": (ctypes.c_int, [_I32, _I32, _I32, _P]),
+    "mcs_sim3_workspace_destroy": (None, [_P]),
+    "mcs_search_by_sim3_device": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_double, _I32,
+                                                 _P, _P, _P, _P, _P]),
+    "mcs_search_by_sim3": (ctypes.c_int, [_I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_double, _I32,
+                                          _P, _P, _P, _P]),
     # DBoW2 vocabulary (include/mcs_vocab.h)
     "mcs_vocab_create": (_I32, [_I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _P, _I32, _P]),
     "mcs_vocab_destroy": (_I32, [_P]),
