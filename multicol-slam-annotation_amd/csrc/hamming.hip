@@ -7,6 +7,7 @@
 #include "common.hpp"
 #include "proj_window.hpp"
 #include "ham_dist.hpp"
+#include "top2_net.hpp"
 #include <map>
 #include <mutex>
 #include "../../include/mcs_matcher.h"
@@ -26,15 +27,9 @@ constexpr int kHamTile = 256;      // train rows per LDS tile
 // Each lane owns kQPT queries (descriptors in VGPRs) so one LDS broadcast read of a train
 // row feeds kQPT distances.  The running best/second-best are kept as packed keys
 // (dist << 16 | train index): trains are scanned in index order, so the strict-< rule of the
-// reference scans (first minimum wins, :2447) equals "two smallest keys", maintained with
-// v_min_u32 + v_med3_u32 (best <= second always).
+// reference scans (first minimum wins, :2447) equals "two smallest keys", maintained four keys
+// at a time with v_min3_u32 / v_med3_u32 (top2_net.hpp; best <= second always).
 constexpr int kQPT = 2;
-
-__device__ __forceinline__ uint32_t med3_u32(uint32_t a, uint32_t b, uint32_t c) {
-  uint32_t r;
-  asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
 
 // popcount-accumulate as one v_bcnt_u32_b32 (the compiler otherwise reassociates the sum
 // into bcnt(x, 0) + v_add3 chains, 25 % more VALU)
@@ -92,7 +87,8 @@ __global__ __launch_bounds__(kHamThreads) void k_top2(
     const uint4* src = reinterpret_cast<const uint4*>(T + (int64_t)t0 * W * 4);
     for (int i = threadIdx.x; i < nt_tile * (W / 4); i += kHamThreads) tile[i] = src[i];
     __syncthreads();
-    auto body = [&](int j) {
+    // the keys of train row j of the tile against this lane's kQPT queries
+    auto keys_of = [&](int j, uint32_t (&key)[kQPT]) {
       const uint4* tr = &tile[j * (W / 4)];
       const uint32_t idx = (uint32_t)(t0 + j);
       uint32_t d[kQPT];
@@ -110,15 +106,21 @@ __global__ __launch_bounds__(kHamThreads) void k_top2(
         }
       }
 #pragma unroll
-      for (int k = 0; k < kQPT; k++) {
-        const uint32_t key = (d[k] << 16) | idx;
-        k2[k] = med3_u32(k1[k], key, k2[k]);
-        k1[k] = min(k1[k], key);
-      }
+      for (int k = 0; k < kQPT; k++) key[k] = (d[k] << 16) | idx;
     };
     int j = 0;
-    for (; j + 4 <= nt_tile; j += 4) { body(j); body(j + 1); body(j + 2); body(j + 3); }
-    for (; j < nt_tile; j++) body(j);
+    for (; j + 4 <= nt_tile; j += 4) {
+      uint32_t ka[kQPT], kb[kQPT], kc[kQPT], kd[kQPT];
+      keys_of(j, ka); keys_of(j + 1, kb); keys_of(j + 2, kc); keys_of(j + 3, kd);
+#pragma unroll
+      for (int k = 0; k < kQPT; k++) top2_update4(k1[k], k2[k], ka[k], kb[k], kc[k], kd[k]);
+    }
+    for (; j < nt_tile; j++) {
+      uint32_t ka[kQPT];
+      keys_of(j, ka);
+#pragma unroll
+      for (int k = 0; k < kQPT; k++) top2_update1(k1[k], k2[k], ka[k]);
+    }
   }
   const int none = 8 * 4 * W + 1;
 #pragma unroll
@@ -311,12 +313,20 @@ __global__ __launch_bounds__(256, MCS_TOP2_MINB) void k_top2_mfma32(
         for (int r = 0; r < 16; r++)
           if (tb + (r & 3) + 8 * (r >> 2) >= nt) { key0[r] = kNone; key1[r] = kNone; }
       }
+      // The compiler pads the wait states between an MFMA and a VALU read of its result only
+      // for instructions it knows, not for the operands of an asm statement (min3_u32).  So the
+      // first reads of both accumulators are plain medians, which the compiler pads, and
+      // nothing is scheduled across the barrier behind them; the first updates below reuse
+      // the two values.
+      const uint32_t lead0 = med3_u32(key0[0], key0[1], key0[2]);
+      const uint32_t lead1 = med3_u32(key1[0], key1[1], key1[2]);
+      asm volatile("" :: "v"(lead0), "v"(lead1));
+      __builtin_amdgcn_sched_barrier(0);
+      // four keys per update: registers 4 g .. 4 g + 2 are the triple, 4 g + 3 the single
 #pragma unroll
-      for (int r = 0; r < 16; r++) {
-        k2[0] = med3_u32(k1[0], key0[r], k2[0]);
-        k1[0] = min(k1[0], key0[r]);
-        k2[1] = med3_u32(k1[1], key1[r], k2[1]);
-        k1[1] = min(k1[1], key1[r]);
+      for (int g = 0; g < 4; g++) {
+        top2_update4(k1[0], k2[0], key0[4 * g], key0[4 * g + 1], key0[4 * g + 2], key0[4 * g + 3]);
+        top2_update4(k1[1], k2[1], key1[4 * g], key1[4 * g + 1], key1[4 * g + 2], key1[4 * g + 3]);
       }
       if (KEYED) {   // re-base the running keys to the next sub-tile
 #pragma unroll
