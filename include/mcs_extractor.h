@@ -101,7 +101,10 @@ int mcs_extract(mcs_extractor* h, const uint8_t* image, int32_t stride, const ui
 
 /* Register static per-camera masks (device memory, n_masks x height x width, pitch =
  * width).  Their pyramids are built once (the reference rebuilds them per frame,
- * src/mdBRIEFextractorOct.cpp:1182-1197).  n_masks = 0 clears. */
+ * src/mdBRIEFextractorOct.cpp:1182-1197).  With masks registered, the ORB batch path
+ * computes a pyramid level and its blur only where an output can depend on them (a mask is a
+ * property of its camera); outputs are unchanged.  The first batch of a new size builds its
+ * work-unit table (a synchronous upload).  n_masks = 0 clears and returns to whole levels. */
 int mcs_extractor_set_masks_device(mcs_extractor* h, const uint8_t* d_masks, int32_t n_masks,
                                    void* stream);
 
@@ -132,7 +135,10 @@ int mcs_extract_batch_device_ex(mcs_extractor* h, const uint8_t* d_images, int32
  * stage 1: 5x5-blurred level image; stage 2: FAST candidates of the level in reference
  * order as int32 triples (x_rel, y_rel, score), coordinates relative to minBorder=22
  * (src/mdBRIEFextractorOct.cpp:876-945); stage 3: octree selection of the level as int32
- * triples in output order.  *n_out = element count (bytes for 0/1, triples for 2/3). */
+ * triples in output order.  *n_out = element count (bytes for 0/1, triples for 2/3).
+ * After a batch with registered masks, stages 0 and 1 are defined only where an output
+ * depends on them (at least wherever the level's mask is set); the rest of the workspace
+ * keeps whatever it held. */
 int mcs_extractor_read_stage(mcs_extractor* h, int32_t stage, int32_t frame, int32_t level,
                              void* dst, int64_t cap, int64_t* n_out);
 

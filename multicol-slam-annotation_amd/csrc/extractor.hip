@@ -14,6 +14,7 @@
 #include "common.hpp"
 #include "extractor_plan.hpp"
 #include "extractor_kernels.hpp"
+#include "pyr_units.hpp"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -56,6 +57,16 @@ struct mcs_extractor {
   uint8_t* d_mask_pyr = nullptr; int n_masks = 0;
   mcs::FastUnit* d_munits = nullptr; int64_t munit_stride = 0;   // per-mask FAST units
   uint8_t* d_mask_single = nullptr;
+  // k_pyr_rows unit tables (pyr_units.hpp), one per batch-size class and kind, built on first
+  // use: full = every pixel (no registered mask, the single-call path, dBRIEF / mdBRIEF, whose
+  // distorted pattern has no fixed reach); masked = per registered mask, from its need set
+  struct PyrTable {
+    int fclass = 0; bool masked = false;
+    mcs::PyrUnit* d_units = nullptr; int64_t mstride = 0;
+    int32_t off[mcs::kMaxLevels] = {}, n[mcs::kMaxLevels] = {};
+  };
+  std::vector<PyrTable> pyr_tabs;
+  std::vector<mcs::PyrNeed> pyr_need;   // per registered mask
   // single-frame staging
   uint8_t* d_in = nullptr;
   mcs_keypoint* d_kps = nullptr; uint8_t* d_desc = nullptr; int32_t* d_count = nullptr;
@@ -86,6 +97,43 @@ static void fill_level_ptrs(const Plan& pl, LevelPtrs& lp) {
   }
 }
 
+// The unit table for batches of F frames (built and uploaded on the first batch of a size
+// class; F >= kPyrFrameClasses share one)
+static int pyr_table(mcs_extractor* h, int F, bool masked, const mcs_extractor::PyrTable** out) {
+  const int fc = pyr_frame_class(F);
+  for (const auto& t : h->pyr_tabs)
+    if (t.fclass == fc && t.masked == masked) { *out = &t; return MCS_OK; }
+  const Plan& pl = h->plan;
+  const int nm = masked ? (int)h->pyr_need.size() : 1;
+  std::vector<std::vector<PyrUnit>> lists((size_t)nm * kMaxLevels);
+  mcs_extractor::PyrTable t;
+  t.fclass = fc; t.masked = masked;
+  for (int m = 0; m < nm; m++) {
+    std::vector<PyrUnit> lv[kMaxLevels];
+    build_pyr_units(pl, masked ? &h->pyr_need[m] : nullptr, fc, lv);
+    for (int l = 0; l < pl.nlevels; l++) {
+      t.n[l] = std::max(t.n[l], (int32_t)lv[l].size());
+      lists[(size_t)m * kMaxLevels + l].swap(lv[l]);
+    }
+  }
+  int64_t stride = 0;
+  for (int l = 0; l < pl.nlevels; l++) { t.off[l] = (int32_t)stride; stride += t.n[l]; }
+  stride = std::max<int64_t>(stride, 1);
+  std::vector<PyrUnit> all((size_t)nm * stride, PyrUnit{0, 0, 0, 0});   // pads: no rows
+  for (int m = 0; m < nm; m++)
+    for (int l = 0; l < pl.nlevels; l++) {
+      const auto& v = lists[(size_t)m * kMaxLevels + l];
+      std::copy(v.begin(), v.end(), all.begin() + (size_t)m * stride + t.off[l]);
+    }
+  int rc = dalloc(&t.d_units, all.size());
+  if (rc) return rc;
+  MCS_HIP_CHECK(hipMemcpy(t.d_units, all.data(), all.size() * sizeof(PyrUnit), hipMemcpyHostToDevice));
+  t.mstride = nm > 1 ? stride : 0;
+  h->pyr_tabs.push_back(t);
+  *out = &h->pyr_tabs.back();
+  return MCS_OK;
+}
+
 static inline void stage_mark(mcs_extractor* h, int stage, hipStream_t st) {
   if (!h->timing || h->ev_count >= mcs_extractor::kRing) return;
   (void)hipEventRecord(h->ev[h->ev_count * (MCS_EXTRACTOR_NSTAGES + 1) + stage], st);
@@ -99,6 +147,14 @@ static int run_batch(mcs_extractor* h, const uint8_t* d_images, int F, const uin
   const Plan& pl = h->plan;
   const int nl = pl.nlevels;
   const int64_t img0_fs = (int64_t)pl.W * pl.H;
+  // registered masks (not the single-call slot) drive both the FAST and the pyramid unit lists
+  const bool per_mask = mask_pyr && mask_pyr == h->d_mask_pyr && h->d_munits;
+  const bool orb = !pl.p.learn_masks && !pl.p.do_dbrief;
+  const mcs_extractor::PyrTable* pt = nullptr;
+  {
+    const int rc = pyr_table(h, F, per_mask && orb && !h->pyr_need.empty(), &pt);
+    if (rc) return rc;
+  }
   auto pyr_args = [&](int l) {
     PyrArgs a;
     const LevelPlan& D = pl.lv[l];
@@ -120,6 +176,8 @@ static int run_batch(mcs_extractor* h, const uint8_t* d_images, int F, const uin
     a.dw = D.w; a.dh = D.h;
     pyr_strips(D.w, D.h, F, a);
     a.nframes = F;
+    a.units = pt->d_units + pt->off[l]; a.nunits = pt->n[l]; a.unit_mstride = pt->mstride;
+    a.mask_index = pt->mstride ? d_mask_index : nullptr; a.nmasks = h->n_masks;
     return a;
   };
   // K2 arguments (row-streaming FAST; one launch per level, units of a level are contiguous)
@@ -166,7 +224,6 @@ static int run_batch(mcs_extractor* h, const uint8_t* d_images, int F, const uin
   stage_mark(h, 2, st);
   {
     FastRowArgs fl = fa;
-    const bool per_mask = mask_pyr && mask_pyr == h->d_mask_pyr && h->d_munits;
     fl.units = per_mask ? h->d_munits : h->d_units;
     fl.nunits = per_mask ? (int)h->munit_stride : (int)pl.fast_units.size();
     fl.unit_mstride = per_mask ? h->munit_stride : 0;
@@ -316,6 +373,8 @@ void mcs_extractor_destroy(mcs_extractor* h) {
   if (h->side) (void)hipStreamDestroy(h->side);
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
   if (h->ev_join) (void)hipEventDestroy(h->ev_join);
+  for (auto& t : h->pyr_tabs)
+    if (t.d_units) (void)hipFree(t.d_units);
   if (h->ev) {
     for (int i = 0; i < mcs_extractor::kRing * (MCS_EXTRACTOR_NSTAGES + 1); i++)
       (void)hipEventDestroy(h->ev[i]);
@@ -376,6 +435,12 @@ int mcs_extractor_set_masks_device(mcs_extractor* h, const uint8_t* d_masks, int
   if (h->d_munits) { MCS_HIP_CHECK(hipFree(h->d_munits)); h->d_munits = nullptr; }
   h->n_masks = 0;
   h->munit_stride = 0;
+  // the per-mask pyramid tables go with the masks (hipFree waits for the kernels reading them)
+  for (auto it = h->pyr_tabs.begin(); it != h->pyr_tabs.end();) {
+    if (it->masked) { MCS_HIP_CHECK(hipFree(it->d_units)); it = h->pyr_tabs.erase(it); }
+    else ++it;
+  }
+  h->pyr_need.clear();
   if (n_masks == 0) return MCS_OK;
   const Plan& pl = h->plan;
   int rc = dalloc(&h->d_mask_pyr, (size_t)n_masks * pl.mask_frame_bytes);
@@ -388,10 +453,13 @@ int mcs_extractor_set_masks_device(mcs_extractor* h, const uint8_t* d_masks, int
   MCS_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
   MCS_HIP_CHECK(hipMemcpy(hm.data(), h->d_mask_pyr, hm.size(), hipMemcpyDeviceToHost));
   std::vector<std::vector<FastUnit>> lists(n_masks);
+  std::vector<PyrNeed> need(n_masks);
   size_t stride = 0;
   for (int m = 0; m < n_masks; m++) {
     std::vector<FastUnit> dead;
     build_masked_units(pl, hm.data() + (size_t)m * pl.mask_frame_bytes, lists[m], dead);
+    // what the pyramid has to compute for frames of this mask (pyr_units.hpp)
+    build_pyr_need(pl, hm.data() + (size_t)m * pl.mask_frame_bytes, lists[m], need[m]);
     lists[m].insert(lists[m].end(), dead.begin(), dead.end());   // heavy units first
     stride = std::max(stride, lists[m].size());
   }
@@ -403,6 +471,7 @@ int mcs_extractor_set_masks_device(mcs_extractor* h, const uint8_t* d_masks, int
   MCS_HIP_CHECK(hipMemcpy(h->d_munits, all.data(), all.size() * sizeof(FastUnit), hipMemcpyHostToDevice));
   h->munit_stride = (int64_t)stride;
   h->n_masks = n_masks;
+  h->pyr_need.swap(need);
   return MCS_OK;
 }
 

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "extractor_plan.hpp"
+#include "pyr_units.hpp"
 
 namespace mcs {
 
@@ -33,41 +34,19 @@ struct PyrArgs {
   int dw, dh;
   const int32_t* xofs; const int16_t* alpha; const int32_t* yofs; const int16_t* beta;
   int simd_end;
-  int tiles_x, tiles_y, nframes;   // tiles_x = column strips, tiles_y = row segments
+  int nframes;
+  // work units of the level (build_pyr_units): wave `u` of frame f takes
+  // units[mask_index[f] * unit_mstride + u]; unit_mstride == 0: one list for every frame
+  const PyrUnit* units; int nunits; int64_t unit_mstride;
+  const int32_t* mask_index; int nmasks;   // index clamped to [0, nmasks)
+  // the full-frame geometry of pyr_strips (not read by the kernel)
+  int tiles_x, tiles_y;            // tiles_x = column strips, tiles_y = row segments
   int core, seg_rows;              // strip width (px, multiple of 4, <= 244), segment height
 };
-// strips of <= 244 columns (61 lanes x 4 px, so a level-0 strip + halo is <= 64 dwords);
-// segment height chosen for ~32 waves per frame, at least 8k waves per launch (latency hiding
-// for small batches), between 8 and 64 rows.  Per frame that is a fixed geometry, so the
-// production step's two halves on two streams (bench.py --split 2: two launches of ~256 frames
-// side by side) cut their segments as tall as one launch of the whole batch; a fixed 16k-wave
-// target had halved the segments of a half (more halo rows per output row).  Round 6:
-// 399 -> 410 M keypoints/s.
+// the geometry rule lives in pyr_units.hpp (host only); the kernel takes its strips and
+// segments from the unit table built with it (build_pyr_units)
 inline void pyr_strips(int dw, int dh, int F, PyrArgs& a) {
-  const int n = (dw + 243) / 244;
-  a.core = ((dw + n - 1) / n + 3) & ~3;
-  a.tiles_x = (dw + a.core - 1) / a.core;
-#ifndef MCS_PYR_TARGET
-#define MCS_PYR_TARGET 8192
-#endif
-#ifndef MCS_PYR_WAVES_PER_FRAME
-#define MCS_PYR_WAVES_PER_FRAME 32
-#endif
-  // (more waves per frame for the levels under 200 rows only, 48 or 64 with segments down to
-  // 6 / 4 rows, and segments down to 4 rows alone measured flat or slower at the end of round 6)
-  const long target = std::max<long>(MCS_PYR_TARGET, (long)MCS_PYR_WAVES_PER_FRAME * (F > 0 ? F : 1));
-  const long per_seg = (long)a.tiles_x * (F > 0 ? F : 1);
-  const int segs = (int)std::max<long>(1, (target + per_seg - 1) / per_seg);
-  int rows = (dh + segs - 1) / segs;
-#ifndef MCS_PYR_MAXROWS
-#define MCS_PYR_MAXROWS 64
-#endif
-#ifndef MCS_PYR_MINROWS
-#define MCS_PYR_MINROWS 8
-#endif
-  rows = std::min(MCS_PYR_MAXROWS, std::max(MCS_PYR_MINROWS, rows));
-  a.seg_rows = rows;
-  a.tiles_y = (dh + rows - 1) / rows;
+  pyr_strip_geometry(dw, dh, F, &a.core, &a.tiles_x, &a.seg_rows, &a.tiles_y);
 }
 // wide: source tiles for scale factors in (1.5, 2.2] (larger LDS footprint)
 void launch_pyr_blur(const PyrArgs& a, bool resize, bool wide, hipStream_t st);

@@ -13,7 +13,8 @@
 namespace mcs {
 
 // Row-streaming pyramid level: one wave owns a strip of `core` (<= 244) output columns and a
-// segment of `seg_rows` rows.  Lane L holds 4 consecutive pixels [xs-4+4L, xs+4L); lane 0 and
+// segment of rows, its PyrUnit from the frame's list (pyr_units.hpp: whole levels, or with
+// registered masks only what an output can depend on).  Lane L holds 4 consecutive pixels [xs-4+4L, xs+4L); lane 0 and
 // the lane after the core are the +-2 px halo of the blur.  A pixel outside the level holds
 // the value of its BORDER_REFLECT_101 mirror (computed from the mirror's own coordinates),
 // so the horizontal 5-sum needs no border cases.  Rows are produced top to bottom with a
@@ -50,15 +51,22 @@ __global__ __launch_bounds__(256, MCS_PYR_OCC) void k_pyr_rows(PyrArgs a) {
   uint32_t* const stage = lds_stage[wv];
   const uint8_t* const stb = reinterpret_cast<const uint8_t*>(stage);
   int f, item;
-  const int units = a.tiles_x * a.tiles_y;
-  if (!xcd_frame_map(blockIdx.x, a.nframes, (units + 3) / 4, &f, &item)) return;
-  const int unit = item * 4 + wv;
-  if (unit >= units) return;
-  const int strip = unit % a.tiles_x, seg = unit / a.tiles_x;
-  const int dw = a.dw, dh = a.dh, core = a.core;
-  const int xs = strip * core;
+  if (!xcd_frame_map(blockIdx.x, a.nframes, (a.nunits + 3) / 4, &f, &item)) return;
+  const int ui = item * 4 + wv;
+  if (ui >= a.nunits) return;
+  // the wave's unit (strip and row segment) from the frame's list: scalar loads, before any
+  // store (after one the compiler could no longer prove them unclobbered and would make them
+  // vector loads).  A pad unit (the shorter lists of other masks) has no rows.
+  const int mi = a.mask_index ? min(max(a.mask_index[f], 0), a.nmasks - 1) : 0;
+  // (read as two dwords: there is no scalar load of a 16-bit field)
+  static_assert(sizeof(PyrUnit) == 8 && alignof(PyrUnit) == 8, "PyrUnit is read as two dwords");
+  const uint2 uw = *reinterpret_cast<const uint2*>(a.units + ((int64_t)mi * a.unit_mstride + ui));
+  const int urows = (int)(int16_t)(uw.y >> 16);
+  if (urows <= 0) return;
+  const int dw = a.dw, dh = a.dh, core = (int)(int16_t)(uw.x >> 16);
+  const int xs = (int)(int16_t)(uw.x & 0xFFFFu);
   const int xcore1 = min(xs + core, dw);           // core px [xs, xcore1)
-  const int seg0 = seg * a.seg_rows, seg1 = min(dh, seg0 + a.seg_rows);
+  const int seg0 = (int)(int16_t)(uw.y & 0xFFFFu), seg1 = min(dh, seg0 + urows);
   const int r_begin = max(0, seg0 - 2), r_end = min(dh, seg1 + 2);
   const int xb = xs - 4 + 4 * lane;                // lane's first pixel
   const bool core_lane = xb >= xs && xb < xcore1;
@@ -324,7 +332,8 @@ __global__ __launch_bounds__(256, MCS_PYR_OCC) void k_pyr_rows(PyrArgs a) {
 }
 
 void launch_pyr_blur(const PyrArgs& a, bool resize, bool wide, hipStream_t st) {
-  const unsigned g = xcd_grid(a.nframes, (a.tiles_x * a.tiles_y + 3) / 4);
+  if (a.nunits <= 0) return;   // no frame needs a pixel of this level
+  const unsigned g = xcd_grid(a.nframes, (a.nunits + 3) / 4);
   if (!resize)
     hipLaunchKernelGGL((k_pyr_rows<false, 1>), dim3(g), dim3(256), 0, st, a);
   else if (!wide)
