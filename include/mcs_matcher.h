@@ -535,6 +535,172 @@ int mcs_search_by_sim3(int32_t device, const mcs_fuse_targets* kf1, const mcs_si
                        const double* R12, const double* t12, double th, int32_t th_high,
                        int32_t* match1, int32_t* match2, int32_t* matches12, int32_t* n_found);
 
+/* ---- cSim3Solver: the loop-closing Sim3 RANSAC ------------------------------------------------
+ *   cSim3Solver::cSim3Solver(pKF1, pKF2, vpMatched12, camSys)     src/cSim3Solver.cpp:44-137
+ *   SetRansacParameters(probability, minInliers, maxIterations)   src/cSim3Solver.cpp:139-165
+ *   iterate(nIterations, bNoMore, vbInliers, nInliers, result)    src/cSim3Solver.cpp:167-254
+ *   find                                                          src/cSim3Solver.cpp:256-262
+ *   centroid, computeT (Horn 1987 on three points)                src/cSim3Solver.cpp:264-371
+ *   CheckInliers                                                  src/cSim3Solver.cpp:374-415
+ * called per loop candidate by cLoopClosing::ComputeSim3 (src/cLoopClosing.cpp:311-364) between
+ * SearchByBoW(KF, KF) and SearchBySim3.  Here ONE current keyframe KF1 against a batch of T
+ * candidates: the constructor, the RANSAC and the hand-over to SearchBySim3 are stream-ordered
+ * device entries, so BoW -> prepare -> iterate -> active -> SearchBySim3 runs with nothing
+ * downloaded.  Keyframes are mcs_fuse_targets sets (kf1 with n_targets == 1, kf2s with the T
+ * candidates), map points mcs_sim3_points of which only pos is read.  Everything is FP64.
+ *
+ * A hypothesis depends on no RANSAC state: every iteration samples afresh from mvAllIndices
+ * (:202).  So one call evaluates all its iterations of all candidates in parallel and only the
+ * acceptance rule (:228-253) is applied in iteration order.  The text draws with
+ * std::random_device, which cannot be reproduced: the ABI takes the sample triples from the
+ * caller.  cv::eigen and cv::Rodrigues are OpenCV internals, so a hypothesis's (s, R, t) is
+ * Horn's solution to rounding (cyclic Jacobi on the 4x4), not bitwise; where the top eigenvalue
+ * of N is not simple (a repeated index, a collinear triple) the text itself does not define the
+ * rotation.  Everything after the hypothesis follows the text's operation order exactly. */
+
+/* The three correspondence indices of each iteration from its three dis(gen) values, exactly as
+ * :202-222 do (host, integers only; no GPU).  vAvailableIndices starts as 0 .. n-1 (mvAllIndices),
+ * the distribution stays 0 .. n-1 while the vector shrinks, and the swap is written to the drawn
+ * VALUE (`vAvailableIndices[idx] = back()`, :220), not to the drawn position: a triple can
+ * repeat an index.  A draw at or past the vector's current size reads out of range in the text;
+ * here the vector is an array of n whose popped elements keep their value, which is what an
+ * unchecked std::vector does.  draws, samples [n_its][3].  MCS_ERR_ARG: n < 3, a draw outside
+ * [0, n), a null buffer. */
+int mcs_sim3_draw_samples(int32_t n, const int32_t* draws, int32_t n_its, int32_t* samples);
+
+/* What the constructor builds, per candidate t, rows t * cap .. t * cap + n[t], cap = n1 =
+ * kf1->n_kp_total, in i1 order (the order of mvnIndices1).  m_c / cam / n_cams are camSysLocal
+ * (:51), the rig CheckInliers projects with (:391-398): the caller sets them, at the call site
+ * to KF1's m_c and cam.  In the host-buffer form the pointers are host outputs, each nullable,
+ * and m_c / cam are ignored (KF1's are taken). */
+typedef struct mcs_sim3_corr {
+  int32_t n_targets, cap, n_cams;
+  const double* m_c;           /* [n_cams][16] */
+  const double* cam;           /* [n_cams][17] c d e u0 v0 invP[12] */
+  int32_t* n;                  /* [T] N = mvpMapPoints1.size() */
+  int32_t* idx1;               /* [T][cap] mvnIndices1 */
+  double* X1;                  /* [T][cap][3] mvX3Dc1 */
+  double* X2;                  /* [T][cap][3] mvX3Dc2 */
+  double* p1;                  /* [T][cap][2] mvP1im1 */
+  double* p2;                  /* [T][cap][2] mvP2im2 */
+  int32_t* cam1;               /* [T][cap] camIdx1 */
+  int32_t* cam2;               /* [T][cap] camIdx2 */
+  double* maxerr1;             /* [T][cap] mvnMaxError1 (whole numbers: the text stores size_t) */
+  double* maxerr2;             /* [T][cap] mvnMaxError2 */
+} mcs_sim3_corr;
+
+/* The solver's members that live across iterate calls (in/out) and the outputs of one call. */
+typedef struct mcs_sim3_ransac {
+  int32_t* iterations;         /* [T] mnIterations */
+  int32_t* best_inliers;       /* [T] mnBestInliers */
+  int32_t* max_its;            /* [T] mRansacMaxIts; 0 when N < min_inliers (the text leaves it undefined) */
+  uint64_t* best_words;        /* [T][(cap + 63) / 64] mvbBestInliers, bit i = correspondence i */
+  double* s12;                 /* [T] mBestScale */
+  double* R12;                 /* [T][9] mBestRotation, row-major */
+  double* t12;                 /* [T][3] mBestTranslation */
+  double* T12;                 /* [T][16] mBestT12 (`result` on a success) */
+  int32_t* success;            /* out [T] the return value */
+  int32_t* no_more;            /* out [T] bNoMore */
+  int32_t* n_inliers;          /* out [T] nInliers */
+  uint8_t* inlier;             /* out [T][cap] vbInliers, scattered through idx1 */
+  double* hyp_srt;             /* out, nullable [T][n_iterations][13] s, R, t of every hypothesis evaluated */
+  int32_t* hyp_inl;            /* out, nullable [T][n_iterations] mnInliersi; -1 = not evaluated */
+} mcs_sim3_ransac;
+
+/* The constructor (:44-137) for all T candidates in one launch.  Device pointers throughout.
+ *   d_matches12 [T][n1]   KF2 keypoint index whose slot holds pMP2 = vpMatched12[i1], -1 = none:
+ *                         the output format of mcs_search_by_bow_kf_device
+ *   d_ok1 [n1]            KF1's slot i1 holds a point that is not bad (:77, :82)
+ *   d_ok2 [n_kp_total of kf2s]  the slot's point is not bad (:82), packed like the candidates
+ *   d_first1 [n1]         (int)GetIndexInKeyFrame(pKF1)[0] of the slot's point, local to the
+ *                         keyframe; -1 when the point does not observe it (src/cMapPoint.cpp:436-445)
+ *   d_first2              the same for the candidates, packed like them
+ *   d_sigma2 [n_levels]   mvLevelSigma2
+ * A slot is skipped without a match, with !ok1, with !ok2 of the matched slot, or when either
+ * first index is negative (:73-98).  Octave, camera and projection are those of keypoint `first`
+ * (idxs[0], :94-125), not of i1 / the matched slot; the positions are those of the slots' points.
+ * X = Hom2R(invMat(M_t)) * Xw + Hom2T(invMat(M_t)) in cv::Matx operation order (:118, :127), p =
+ * WorldToCamHom_fast in the camera of keypoint `first` (:116, :125), maxerr = 9.210 * sigma2[octave
+ * of keypoint first] truncated toward zero (:106-107: mvnMaxError1 / 2 are std::vector<size_t>,
+ * include/cSim3Solver.h:92-93; CheckInliers compares against the integer as a double).  Rows are compacted in i1 order (a ballot prefix, no atomics).
+ * Indices that are device data are clamped: a match or first index outside its keyframe, an octave
+ * outside [0, n_levels) or a camera outside [0, n_cams) skips the slot (the text reads out of range
+ * there).  Stream-ordered, no host synchronisation, no allocation.  MCS_ERR_ARG: kf1->n_targets !=
+ * 1, n_cams / n_levels differing between the sets, more than 8 cameras, a KF1 of 2^19 keypoints or
+ * more, points not matching their set, corr's n_targets / cap / n_cams not T / n1 / n_cams, a null
+ * buffer. */
+int mcs_sim3_solver_prepare_device(const mcs_fuse_targets* kf1, const mcs_sim3_points* pts1,
+                                   const mcs_fuse_targets* kf2s, const mcs_sim3_points* pts2,
+                                   const int32_t* d_matches12, const uint8_t* d_ok1,
+                                   const uint8_t* d_ok2, const int32_t* d_first1,
+                                   const int32_t* d_first2, const double* d_sigma2,
+                                   const mcs_sim3_corr* corr, void* stream);
+
+/* Device scratch of mcs_sim3_solver_iterate_device for <= max_targets candidates of <= max_kp
+ * correspondences and calls of <= max_its_cap iterations: the hypotheses, their inlier words and
+ * counts, invMat(M_c). */
+typedef struct mcs_sim3_solver_workspace mcs_sim3_solver_workspace;
+int mcs_sim3_solver_workspace_create(int32_t device, int32_t max_targets, int32_t max_kp,
+                                     int32_t max_its_cap, mcs_sim3_solver_workspace** out);
+void mcs_sim3_solver_workspace_destroy(mcs_sim3_solver_workspace* ws);
+
+#define MCS_SIM3_SET_PARAMS 1   /* SetRansacParameters (:139-165): max_its from n[t], iterations = 0 */
+#define MCS_SIM3_INIT 2         /* the constructor's state (:48-49) as well: best_inliers = 0, mBest* = 0 */
+
+/* iterate (:167-254) for all candidates: iterations [iterations[t], min(iterations[t] +
+ * n_iterations, max_its[t])) of every candidate in four launches (parameters and invMat(M_c);
+ * computeT per (candidate, iteration); CheckInliers with lanes over correspondences and the rows
+ * staged per block; the acceptance rule, one wave per candidate).
+ *   d_samples [T][max_its_cap][3]  the correspondence indices of iteration k of candidate t
+ *                                  (mcs_sim3_draw_samples), any value in [0, n[t]), repeats included
+ *   flags  MCS_SIM3_INIT at the first call after prepare, MCS_SIM3_SET_PARAMS for a later
+ *          SetRansacParameters, 0 to go on.  max_its = max(1, min(ceil(log(1 - prob) /
+ *          log(1 - pow(min_inliers / N, 3))), max_its_cap)), 1 when N == min_inliers, computed on
+ *          the device from n[t]; max_its_cap where pow(.., 3) underflows against 1 (the text's int
+ *          conversion of -inf is undefined there).  For N < min_inliers iterate returns at :177 whatever
+ *          mRansacMaxIts holds: max_its = 0, no_more = 1, success = 0.
+ * The running best updates when mnInliersi >= mnBestInliers (:228: ties take the later
+ * iteration); a hit is the first iteration that does so with mnInliersi > min_inliers (:237), and
+ * iterations stops behind it; no_more = no hit in this call and iterations >= max_its (:250).
+ * mBest* are updated whenever the text updates them, also without a hit.  find (:256-262) is
+ * n_iterations = max_its_cap.  A NaN hypothesis (a repeated index gives den == 0) has no inliers.
+ * Launch sizes come from T, n_iterations and cap only.  Stream-ordered, no host synchronisation,
+ * no allocation with a workspace; ws NULL = a temporary one is allocated and freed (which
+ * synchronises).  Counts, indices and cameras in corr and d_samples are device data and are
+ * clamped.  MCS_ERR_ARG: n_iterations outside [1, max_its_cap], min_inliers < 1, prob outside
+ * (0, 1), an unknown flag, more than the workspace holds, a null buffer. */
+int mcs_sim3_solver_iterate_device(mcs_sim3_solver_workspace* ws, const mcs_sim3_corr* corr,
+                                   const int32_t* d_samples, int32_t n_iterations, double prob,
+                                   int32_t min_inliers, int32_t max_its_cap, int32_t flags,
+                                   const mcs_sim3_ransac* ransac, void* stream);
+
+/* The hand-over to SearchBySim3: d_active1 [T][n1] and d_active2 (packed like the candidates) as
+ * src/cORBmatcher.cpp:1758-1774 and the loops' skip conditions see them when vpMatches12 holds
+ * the inliers' entries alone (src/cLoopClosing.cpp:354-360).  d_good1 [n1] / d_good2 (packed):
+ * the slot holds a map point that is not bad.  active1 = good1 && !inlier; active2 = good2,
+ * cleared at first2 of the slot every inlier is matched to, when that lies in [0, N2).  Two
+ * launches, stream-ordered. */
+int mcs_sim3_solver_active_device(const mcs_fuse_targets* kf1, const mcs_fuse_targets* kf2s,
+                                  const uint8_t* d_inlier, const uint8_t* d_good1,
+                                  const uint8_t* d_good2, const int32_t* d_matches12,
+                                  const int32_t* d_first2, uint8_t* d_active1, uint8_t* d_active2,
+                                  void* stream);
+
+/* Host-buffer form for the call site (src/cLoopClosing.cpp:311-364): uploads, runs prepare,
+ * iterate and (when active1 / active2 are given) the hand-over on `device`, downloads.  Of the
+ * keyframe sets off, kp_octave, kp_cam, m_t, m_c and cam are read.  samples [T][max_its_cap][3];
+ * corr nullable; the state arrays of `ransac` are host in/out (read unless flags has
+ * MCS_SIM3_INIT).  Also MCS_ERR_ARG for malformed offsets; all argument errors are returned
+ * before any device use.  MCS_ERR_NO_DEVICE without a GPU. */
+int mcs_sim3_solver(int32_t device, const mcs_fuse_targets* kf1, const mcs_sim3_points* pts1,
+                    const mcs_fuse_targets* kf2s, const mcs_sim3_points* pts2,
+                    const int32_t* matches12, const uint8_t* ok1, const uint8_t* ok2,
+                    const int32_t* first1, const int32_t* first2, const double* sigma2,
+                    const int32_t* samples, int32_t n_iterations, double prob, int32_t min_inliers,
+                    int32_t max_its_cap, int32_t flags, const mcs_sim3_corr* corr,
+                    const mcs_sim3_ransac* ransac, const uint8_t* good1, const uint8_t* good2,
+                    uint8_t* active1, uint8_t* active2);
+
 #ifdef __cplusplus
 }
 #endif

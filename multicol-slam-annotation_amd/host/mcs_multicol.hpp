@@ -20,6 +20,7 @@
 #include <cstdint>
 #include <cmath>
 #include <cstring>
+#include <random>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -607,5 +608,126 @@ inline std::vector<int> SearchBySim3(const FuseRig& rig, const Sim3KeyFrame& kf1
       if (m12[(size_t)t * n1 + i] >= 0) cands[t].matches12[i] = m12[(size_t)t * n1 + i];
   return std::vector<int>(nf.begin(), nf.begin() + T);
 }
+
+// cSim3Solver (src/cSim3Solver.cpp) at cLoopClosing::ComputeSim3 (src/cLoopClosing.cpp:311-364):
+// one solver per loop candidate with the reference's surface, on mcs_sim3_solver.  The solver's
+// members (mnIterations, mnBestInliers, mRansacMaxIts, mvbBestInliers, mBest*) are kept between
+// calls as host copies and handed to the library each time, so the 50-iterations-per-visit loop
+// of ComputeSim3 works unchanged, a second iterate after a success included.  The text draws from
+// std::random_device inside iterate; here the draws of all maxIterations iterations come from one
+// std::mt19937 + std::uniform_int_distribution<>(0, N - 1), three per iteration in iteration
+// order, through mcs_sim3_draw_samples.  With N < 3 no triple can be drawn: every sample is 0.
+// The solver keeps references to rig, kf1 and kf2 (as the text keeps pKF1 / pKF2): they must outlive
+// it.  Every iterate uploads the keyframes and runs the constructor's kernel again; callers that
+// visit often use the device entries, which keep everything resident.
+class Sim3Solver {
+ public:
+  // matches12 [n1]: vpMatched12 as a keypoint of kf2 (its slot's map point), -1 = NULL.
+  // first1 [n1] / first2 [n2]: (int)GetIndexInKeyFrame(pKF)[0] of the slot's point, -1 when it
+  // observes nothing.  sigma2: mvLevelSigma2.  camSys is KF1's rig, as at the call site.
+  Sim3Solver(const FuseRig& rig, const Sim3KeyFrame& kf1, const Sim3KeyFrame& kf2,
+             const std::vector<int32_t>& matches12, const std::vector<int32_t>& first1,
+             const std::vector<int32_t>& first2, const std::vector<double>& sigma2,
+             unsigned seed = std::random_device{}(), int device = 0)
+      : rig_(rig), kf1_(kf1), kf2_(kf2), m12_(matches12), f1_(first1), f2_(first2), sigma2_(sigma2), gen_(seed),
+        device_(device) {
+    if (!kf1.kf || !kf2.kf) throw std::invalid_argument("Sim3Solver: a keyframe is missing");
+    n1_ = (int)kf1.kf->kp_octave.size();
+    n2_ = (int)kf2.kf->kp_octave.size();
+    if ((int)m12_.size() != n1_ || (int)f1_.size() != n1_ || (int)f2_.size() != n2_ || (int)kf1.has_mp.size() != n1_ ||
+        (int)kf1.bad.size() != n1_ || (int)kf2.bad.size() != n2_ || (int)sigma2_.size() != (int)rig.scale.size())
+      throw std::invalid_argument("Sim3Solver: matches12 / first / bad / sigma2 do not fit the keyframes");
+    ok1_.resize(n1_); ok2_.resize(n2_);
+    for (int i = 0; i < n1_; i++) ok1_[i] = kf1.has_mp[i] && !kf1.bad[i];    // :77, :82
+    for (int i = 0; i < n2_; i++) ok2_[i] = !kf2.bad[i];                      // :82
+    N_ = 0;                                                                   // the skip rules of :73-98
+    const int L = (int)rig.scale.size(), C = rig.n_cams;
+    for (int i = 0; i < n1_; i++) {
+      const int m = m12_[i];
+      if (m < 0 || m >= n2_ || !ok1_[i] || !ok2_[m] || f1_[i] < 0 || f1_[i] >= n1_ || f2_[m] < 0 || f2_[m] >= n2_) continue;
+      const int o1 = kf1.kf->kp_octave[f1_[i]], o2 = kf2.kf->kp_octave[f2_[m]];
+      const int c1 = kf1.kf->kp_cam[f1_[i]], c2 = kf2.kf->kp_cam[f2_[m]];
+      N_ += o1 >= 0 && o1 < L && o2 >= 0 && o2 < L && c1 >= 0 && c1 < C && c2 >= 0 && c2 < C;
+    }
+    words_.assign((size_t)(n1_ + 63) / 64 + 1, 0);
+    flags_ = MCS_SIM3_INIT;
+    SetRansacParameters();                                                    // :136
+  }
+
+  void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {
+    if (maxIterations < 1) throw std::invalid_argument("Sim3Solver: maxIterations must be at least 1");
+    prob_ = probability; min_ = minInliers; cap_ = maxIterations;
+    flags_ |= MCS_SIM3_SET_PARAMS;
+    samples_.assign(3 * (size_t)cap_, 0);
+    if (N_ >= 3) {
+      std::uniform_int_distribution<> dis(0, N_ - 1);
+      std::vector<int32_t> draws(3 * (size_t)cap_);
+      for (int32_t& d : draws) d = dis(gen_);
+      check(mcs_sim3_draw_samples(N_, draws.data(), cap_, samples_.data()), "mcs_sim3_draw_samples");
+    }
+  }
+
+  // result: 16 doubles, row-major T12; written on a success only, as the text does
+  bool iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers, double* result) {
+    bNoMore = false;
+    vbInliers.assign(n1_, false);
+    nInliers = 0;
+    if (nIterations < 1) {                                                    // the loop of :196 does not run
+      bNoMore = flags_ == 0 && its_ >= max_its_;
+      return false;
+    }
+    const int32_t L = (int32_t)rig_.scale.size(), C = rig_.n_cams, one[2] = {0, n1_}, two[2] = {0, n2_};
+    const FuseKeyFrame &a = *kf1_.kf, &b = *kf2_.kf;
+    mcs_fuse_targets s1{1, n1_, C, 32, L, rig_.mirror_w, rig_.mirror_h, one, nullptr, a.kp_octave.data(),
+                        a.kp_cam.data(), nullptr, nullptr, nullptr, a.m_t, rig_.m_c.data(), rig_.cam.data(), nullptr,
+                        nullptr, nullptr, nullptr, nullptr};
+    mcs_fuse_targets s2{1, n2_, C, 32, L, rig_.mirror_w, rig_.mirror_h, two, nullptr, b.kp_octave.data(),
+                        b.kp_cam.data(), nullptr, nullptr, nullptr, b.m_t, rig_.m_c.data(), rig_.cam.data(), nullptr,
+                        nullptr, nullptr, nullptr, nullptr};
+    mcs_sim3_points p1{n1_, kf1_.pos.data(), nullptr, nullptr, nullptr}, p2{n2_, kf2_.pos.data(), nullptr, nullptr, nullptr};
+    int32_t ok = 0, no_more = 0, n_inl = 0;
+    std::vector<uint8_t> inl((size_t)n1_ + 1);
+    mcs_sim3_ransac r{&its_, &best_, &max_its_, words_.data(), &s_, R_, t_, T_, &ok, &no_more, &n_inl, inl.data(),
+                      nullptr, nullptr};
+    check(mcs_sim3_solver(device_, &s1, &p1, &s2, &p2, m12_.data(), ok1_.data(), ok2_.data(), f1_.data(), f2_.data(),
+                          sigma2_.data(), samples_.data(), nIterations < cap_ ? nIterations : cap_, prob_, min_, cap_,
+                          flags_, nullptr, &r, nullptr, nullptr, nullptr, nullptr), "mcs_sim3_solver");
+    flags_ = 0;
+    bNoMore = no_more != 0;
+    if (ok) {
+      nInliers = n_inl;
+      for (int i = 0; i < n1_; i++) vbInliers[i] = inl[i] != 0;
+      if (result) std::memcpy(result, T_, sizeof(T_));
+    }
+    return ok != 0;
+  }
+
+  bool find(std::vector<bool>& vbInliers12, int& nInliers, double* result) {
+    bool flag;
+    return iterate(cap_, flag, vbInliers12, nInliers, result);               // :261: mRansacMaxIts <= maxIterations
+  }
+
+  const double* GetEstimatedRotation() const { return R_; }                   // [9] row-major
+  const double* GetEstimatedTranslation() const { return t_; }                // [3]
+  double GetEstimatedScale() const { return s_; }
+  int N() const { return N_; }
+  const std::vector<int32_t>& samples() const { return samples_; }   // [maxIterations][3], iteration k's triple
+  int iterations() const { return its_; }
+  int max_iterations() const { return max_its_; }
+
+ private:
+  const FuseRig& rig_;
+  const Sim3KeyFrame &kf1_, &kf2_;
+  std::vector<int32_t> m12_, f1_, f2_;
+  std::vector<double> sigma2_;
+  std::mt19937 gen_;
+  int device_, n1_ = 0, n2_ = 0, N_ = 0, flags_ = 0, min_ = 6, cap_ = 300;
+  double prob_ = 0.99;
+  std::vector<uint8_t> ok1_, ok2_;
+  std::vector<int32_t> samples_;
+  std::vector<uint64_t> words_;
+  int32_t its_ = 0, best_ = 0, max_its_ = 0;
+  double s_ = 0, R_[9] = {0}, t_[3] = {0}, T_[16] = {0};
+};
 
 }  // namespace mcs

@@ -176,6 +176,14 @@ SIGNATURES = {
                                                  _P, _P, _P, _P, _P]),
     "mcs_search_by_sim3": (ctypes.c_int, [_I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_double, _I32,
                                           _P, _P, _P, _P]),
+    # cSim3Solver (include/mcs_matcher.h; wrappers in mcs_amd/sim3_solver.py)
+    "mcs_sim3_draw_samples": (ctypes.c_int, [_I32, _P, _I32, _P]),
+    "mcs_sim3_solver_workspace_create": (ctypes.c_int, [_I32, _I32, _I32, _I32, _P]),
+    "mcs_sim3_solver_workspace_destroy": (None, [_P]),
+    "mcs_sim3_solver_prepare_device": (ctypes.c_int, [_P] * 12),
+    "mcs_sim3_solver_iterate_device": (ctypes.c_int, [_P, _P, _P, _I32, ctypes.c_double, _I32, _I32, _I32, _P, _P]),
+    "mcs_sim3_solver_active_device": (ctypes.c_int, [_P] * 10),
+    "mcs_sim3_solver": (ctypes.c_int, [_I32] + [_P] * 11 + [_I32, ctypes.c_double, _I32, _I32, _I32] + [_P] * 6),
     # DBoW2 vocabulary (include/mcs_vocab.h)
     "mcs_vocab_create": (_I32, [_I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _P, _I32, _P]),
     "mcs_vocab_destroy": (_I32, [_P]),

@@ -1,0 +1,437 @@
+"""cSim3Solver on the device (mcs_sim3_solver_prepare_device, mcs_sim3_solver_iterate_device,
+mcs_sim3_solver_active_device, mcs_sim3_solver; reference src/cSim3Solver.cpp) against the NumPy
+restatement of tests/test_sim3solver_ref.py.
+
+Stage A (Horn): the device's (s, R, t) of every evaluated hypothesis against np_horn (eigh), where
+the text defines it (three distinct indices, eigenvalue gap above GAP), to TOL_A = 10 x the spread
+between the two CPU restatements.
+Stage B (exact): from the device's own (s, R, t) of each hypothesis the restatement builds T12 /
+T21 and runs CheckInliers; the device's counts must equal it, except that a decision within MARGIN
+(relative) of maxerr may go either way (sure <= count <= sure + unsure; at most 1e-4 of all
+decisions, none in a hit hypothesis).  Then the acceptance rule is replayed over the device's counts:
+success, no_more, iterations, best_inliers, n_inliers, vbInliers, mvbBestInliers, mBest*, max_its,
+active1 and active2 must be exact.  The constructor's rows are exact except p1 / p2, which pass
+through atan (1e-9 px).  Guard bytes surround every output buffer of every run.
+"""
+import ctypes
+
+import numpy as np
+import pytest
+
+from tests.test_sim3solver_ref import (BOUNDARY, CAP, CTOR_SEEDS, GAP, MIN_INL, N_SINGLE, PROB, TOL_A, boundary_case, get_case, load_ctor_scenario, load_iterate, np_active,
+                                       np_check, np_good_flags, np_horn, np_max_its, np_replay, np_transforms, same_as_text, srt_diff)
+
+pytestmark = pytest.mark.gpu
+GUARD = 256                   # bytes of 0x5A around every output buffer
+
+
+def _ss():
+    from mcs_amd import sim3_solver
+    return sim3_solver
+
+
+class Guarded:
+    """Device tensors by name, each the middle of a byte buffer filled with 0x5A."""
+
+    def __init__(self, shapes, skip=()):
+        import torch
+        self.bufs, self.t = {}, {}
+        for k, (dt, shp) in shapes.items():
+            if k in skip:
+                continue
+            nb = int(np.prod(shp)) * np.dtype(dt).itemsize
+            b = torch.full((nb + 2 * GUARD,), 0x5A, dtype=torch.uint8, device="cuda")
+            td = getattr(torch, np.dtype(np.int64 if dt is np.uint64 else dt).name)
+            self.bufs[k], self.t[k] = (b, nb), b[GUARD:GUARD + nb].view(td).view(shp)
+
+    def check(self):
+        for k, (b, nb) in self.bufs.items():
+            h = b.cpu().numpy()
+            assert (h[:GUARD] == 0x5A).all() and (h[GUARD + nb:] == 0x5A).all(), k
+
+    def np(self, k):
+        a = self.t[k].cpu().numpy()
+        return a.view(np.uint64) if k == "best_words" else a
+
+
+class Device:
+    """One solver on the device entries: prepare at construction, then iterate calls."""
+
+    def __init__(self, case, ws=None, good=None, samples=None):
+        import torch
+        ss = _ss()
+        self.case, self.ws = case, ws
+        c = case
+        pk1, pp1, pk2, pp2, m12, o1, o2, f1, f2 = ss.pack_call(c["rig"], c["kf1"], c["pts1"], c["kf2s"], c["pts2s"],
+                                                                c["matches12"], c["ok1"], c["ok2s"], c["first1"], c["first2s"])
+        self.k1, self.p1, self.keep1 = ss.device_sets(pk1, pp1)
+        self.k2, self.p2, self.keep2 = ss.device_sets(pk2, pp2)
+        self.T, self.n1, self.n2, self.off = len(c["kf2s"]), pk1["n_kp_total"], pk2["n_kp_total"], pk2["off"]
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+        self.m12, self.ok1, self.ok2, self.f1, self.f2 = (up(a) for a in (m12, o1, o2, f1, f2))
+        self.sigma2 = up(np.asarray(c["sigma2"], np.float64))
+        self.samples = up(np.asarray(c["samples"] if samples is None else samples, np.int32))
+        self.gc = Guarded(ss.corr_shapes(self.T, self.n1))
+        self.corr, _ = ss.new_corr(self.k1, self.T, given=self.gc.t)
+        ss.prepare_device(self.k1, self.p1, self.k2, self.p2, self.m12, self.ok1, self.ok2, self.f1, self.f2,
+                          self.sigma2, self.corr)
+        self.good = good
+        if good is not None:
+            self.g1, self.g2 = up(good[0]), up(np.concatenate(good[1]) if self.T else np.zeros(0, np.uint8))
+        self.state = None
+
+    def iterate(self, n_it, flags):
+        """-> dict of numpy outputs of this call (state arrays included)."""
+        import torch
+        ss = _ss()
+        shapes = ss.ransac_shapes(self.T, self.n1, n_it)
+        g = Guarded(shapes)
+        if self.state is not None:                       # carry the state tensors over
+            for k in ("iterations", "best_inliers", "max_its", "best_words", "s12", "R12", "t12", "T12"):
+                g.t[k].copy_(self.state.t[k])
+        ran, _ = ss.new_ransac(self.T, self.n1, n_it, given=g.t)
+        ss.iterate_device(self.ws, self.corr, self.samples, n_it, PROB, MIN_INL, CAP, flags, ran)
+        ga = None
+        if self.good is not None:
+            ga = Guarded({"active1": (np.uint8, (self.T, self.n1)), "active2": (np.uint8, (self.n2,))})
+            ss.active_device(self.k1, self.k2, g.t["inlier"], self.g1, self.g2, self.m12, self.f2, ga.t["active1"],
+                             ga.t["active2"])
+        torch.cuda.synchronize()
+        g.check()
+        self.gc.check()
+        self.state = g
+        out = {k: g.np(k) for k in shapes}
+        if ga is not None:
+            ga.check()
+            a2 = ga.np("active2")
+            out["active1"], out["active2"] = ga.np("active1"), [a2[self.off[t]:self.off[t + 1]] for t in range(self.T)]
+        return out
+
+    def rows(self):
+        return {k: self.gc.np(k) for k in self.gc.t}
+
+
+def same_rows(case, got):
+    """The constructor's outputs: exact, p1 / p2 (atan) to 1e-9 px."""
+    for t, want in enumerate(case["rows"]):
+        n = want["n"]
+        assert got["n"][t] == n
+        for k in ("idx1", "cam1", "cam2", "X1", "X2", "maxerr1", "maxerr2"):
+            assert np.array_equal(got[k][t][:n], want[k]), (t, k)
+        for k in ("p1", "p2"):
+            assert np.abs(got[k][t][:n] - want[k]).max(initial=0.0) <= 1e-9, (t, k)
+
+
+class Tracker:
+    """The solver's members per candidate as the replay predicts them."""
+
+    def __init__(self, case):
+        self.case = case
+        T = len(case["kf2s"])
+        self.its, self.best = [0] * T, [0] * T
+        self.max_its = [np_max_its(r["n"])[0] for r in case["rows"]]
+        self.vals = [None] * T                           # (s12, R12, t12, T12, best_words) once updated
+        self.stats = dict(decisions=0, unsure=0, compared=0, evaluated=0)
+        self.sols = [[] for _ in range(T)]               # per call: what coverage() reads
+
+    def check(self, out, n_it, good=None):
+        case = self.case
+        T, n1 = len(case["kf2s"]), len(case["kf1"]["kp_xy"])
+        W = (n1 + 63) // 64
+        for t in range(T):
+            rows = case["rows"][t]
+            N, mx = rows["n"], self.max_its[t]
+            assert out["max_its"][t] == mx
+            k0 = self.its[t]
+            nv = max(min(n_it, mx - k0), 0)
+            assert (out["hyp_inl"][t][nv:] == -1).all() and (out["hyp_inl"][t][:nv] >= 0).all()
+            counts, checks = [], []
+            for k in range(nv):
+                h = out["hyp_srt"][t][k]
+                tri = case["samples"][t][k0 + k]
+                self.stats["evaluated"] += 1
+                if len(set(int(x) for x in tri)) == 3:
+                    ref = np_horn(rows["X1"], rows["X2"], tri)
+                    if ref[3] > GAP:                                                  # stage A
+                        self.stats["compared"] += 1
+                        d = srt_diff((h[0], h[1:10].reshape(3, 3), h[10:13]), ref)
+                        assert d <= TOL_A, (t, k0 + k, d)
+                inl, unsure, f1, f2 = np_check(case["rig"], rows, h[0], h[1:10].reshape(3, 3), h[10:13])   # stage B
+                sure, nu = int((inl & ~unsure).sum()), int(unsure.sum())
+                cnt = int(out["hyp_inl"][t][k])
+                assert sure <= cnt <= sure + nu, (t, k0 + k, cnt, sure, nu)
+                self.stats["decisions"] += N
+                self.stats["unsure"] += nu
+                counts.append(cnt)
+                checks.append((inl, unsure, f1, f2))
+            ok, no_more, its, best, kb = np_replay(counts, k0, self.best[t], mx)
+            self.sols[t].append(dict(success=ok, khit=kb, first=k0, checks=checks))
+            assert bool(out["success"][t]) == ok and bool(out["no_more"][t]) == no_more, (t, k0)
+            assert out["iterations"][t] == its and out["best_inliers"][t] == best
+            if kb is not None:
+                h = out["hyp_srt"][t][kb]
+                sR, tt, _, _ = np_transforms(h[0], h[1:10], h[10:13])
+                T12 = np.eye(4)
+                T12[:3, :3], T12[:3, 3] = sR, tt
+                words = np.zeros(W, np.uint64)
+                assert checks[kb][1].sum() == 0 or not ok                           # no unsure decision in a hit
+                for i in np.flatnonzero(checks[kb][0]):
+                    words[i >> 6] |= np.uint64(1) << np.uint64(i & 63)
+                self.vals[t] = (h[0], h[1:10].copy(), h[10:13].copy(), T12.ravel(), words,
+                                checks[kb][1].sum() == 0)
+            if self.vals[t] is not None:
+                s, R, tt, T12, words, exact = self.vals[t]
+                for k, w in (("s12", s), ("R12", R), ("t12", tt), ("T12", T12)):
+                    assert np.array_equal(out[k][t], w, equal_nan=True), (t, k)
+                if exact:
+                    assert np.array_equal(out["best_words"][t], words)
+            else:
+                assert out["s12"][t] == 0 and (out["best_words"][t] == 0).all()
+            want = np.zeros(n1, np.uint8)
+            if ok:
+                assert out["n_inliers"][t] == counts[kb]
+                want[rows["idx1"][checks[kb][0]]] = 1
+            else:
+                assert out["n_inliers"][t] == 0
+            assert np.array_equal(out["inlier"][t], want)
+            self.its[t], self.best[t] = its, best
+        if good is not None:
+            a1, a2 = np_active(case, out["inlier"], good[0], good[1])
+            assert np.array_equal(out["active1"], a1)
+            assert all(np.array_equal(x, y) for x, y in zip(out["active2"], a2))
+
+    def done(self, single=False):
+        """single: one candidate cannot show both a hit and a candidate without one; the other
+        conditions hold for it too."""
+        s = self.stats
+        assert s["unsure"] <= 1e-4 * max(s["decisions"], 1)
+        assert s["evaluated"] - s["compared"] <= max(0.1 * s["evaluated"], 1)
+        flat = [x for per in self.sols for x in per]
+        late = any(x["success"] and x["khit"] + x["first"] > 0 for x in flat)
+        none = any(not any(x["success"] for x in per) for per in self.sols)
+        f1 = any(c[2].any() for x in flat for c in x["checks"])
+        f2 = any(c[3].any() for x in flat for c in x["checks"])
+        skipped = any((self.case["matches12"][t] >= 0).sum() > self.case["rows"][t]["n"] for t in range(len(self.sols)))
+        assert (late and none or single) and f1 and f2 and skipped, (late, none, f1, f2, skipped)
+
+
+def host_find(case, n_it, flags, state=None, good=None):
+    ss = _ss()
+    c = case
+    return ss.sim3_solver(c["rig"], c["kf1"], c["pts1"], c["kf2s"], c["pts2s"], c["matches12"], c["ok1"], c["ok2s"],
+                          c["first1"], c["first2s"], c["sigma2"], c["samples"], n_it, PROB, MIN_INL, CAP, flags, state,
+                          good[0] if good else None, good[1] if good else None)
+
+
+@pytest.mark.parametrize("N", sorted(BOUNDARY))
+def test_correspondence_counts_with_find(gpu, N):
+    """Candidate 0 has exactly N correspondences, beside companions of 40 and 20, through find
+    (n_iterations = the cap), device entry and host entry: N below / at / above min_inliers, the
+    wave and chunk boundaries of the check kernel, max_its 0, 1, 3, 288 (below the cap) and 300 (at
+    it).  Every batch must show all five coverage conditions."""
+    case = boundary_case(N)
+    good = np_good_flags(case, N)
+    dev = Device(case, good=good)
+    same_rows(case, dev.rows())
+    tr = Tracker(case)
+    tr.check(dev.iterate(CAP, _ss().INIT), CAP, good)
+    tr.done()
+    out = host_find(case, CAP, _ss().INIT, good=good)
+    same_rows(case, out)
+    th = Tracker(case)
+    th.check(out, CAP, good)
+    th.done()
+    assert tr.its == th.its and tr.best == th.best
+    assert tr.max_its[0] == {0: 0, 14: 0, 15: 1, 16: 3, 63: 288}.get(N, CAP)
+
+
+@pytest.mark.parametrize("seed", CTOR_SEEDS)
+def test_constructor_equals_the_reference_text(gpu, seed):
+    """The constructor scenarios of tests/golden/sim3solver_ref.npz through the device entry and the
+    host entry: the rows are the reference text's (p1 / p2 pass through atan: 1e-9 px), and max_its
+    under the constructor's default parameters is the text's."""
+    ss = _ss()
+    case, want = load_ctor_scenario(seed)
+    case["samples"] = np.zeros((1, CAP, 3), np.int32)
+    dev = Device(case)
+    same_as_text({k: (v[0] if k != "n" else int(v[0])) for k, v in dev.rows().items()}, want, 1e-9)
+    c = case
+    out = ss.sim3_solver(c["rig"], c["kf1"], c["pts1"], c["kf2s"], c["pts2s"], c["matches12"], c["ok1"], c["ok2s"], c["first1"],
+                         c["first2s"], c["sigma2"], c["samples"], 1, 0.99, 6, CAP, ss.INIT)
+    same_as_text({k: (out[k][0] if k != "n" else int(out[k][0])) for k in ("n", "idx1", "cam1", "cam2", "maxerr1", "maxerr2",
+                                                                          "X1", "X2", "p1", "p2")}, want, 1e-9)
+    assert out["max_its"][0] == want["max_its_default"]
+
+
+def test_n50_runs_143_iterations_below_the_cap(gpu):
+    """N = 50 gives max_its = 143: find on the device and through the host entry, each iteration
+    checked, in visits of 50 until bNoMore as well."""
+    case = get_case("t1_n50")
+    ss = _ss()
+    tr = Tracker(case)
+    tr.check(Device(case).iterate(CAP, ss.INIT), CAP)
+    th = Tracker(case)
+    th.check(host_find(case, CAP, ss.INIT), CAP)
+    assert tr.max_its == [143] and th.max_its == [143]
+    dev, tc = Device(case), Tracker(case)
+    for call in range(143):                              # a visit ends at a hit, so more than three are needed
+        out = dev.iterate(50, ss.INIT if call == 0 else 0)
+        tc.check(out, 50)
+        if out["no_more"][0]:
+            break
+    assert tc.its == [143] and out["no_more"][0] == 1 and out["iterations"][0] == 143
+    tc.done(single=True)
+
+
+@pytest.mark.parametrize("name", ["t3_mixed", "t3_small"])
+def test_batch_of_three_chunked_equals_find(gpu, name):
+    """T = 3 with different N per candidate, in calls of 50 as ComputeSim3 makes them (a second
+    iterate after a success included) and as one find: every call equals the replay, and each
+    candidate's first success or its bNoMore is the same event in both."""
+    case = get_case(name)
+    ss = _ss()
+    good = np_good_flags(case, 3)
+    ws = ss.Workspace(3, 256, CAP)
+    one = Device(case, ws=ws, good=good)
+    same_rows(case, one.rows())
+    tf = Tracker(case)
+    find = one.iterate(CAP, ss.INIT)
+    tf.check(find, CAP, good)
+    tf.done()
+    dev = Device(case, ws=ws, good=good)
+    tr, first = Tracker(case), [None] * 3
+    for call in range(CAP // 50):
+        out = dev.iterate(50, ss.INIT if call == 0 else 0)
+        tr.check(out, 50, good)
+        for t in range(3):
+            if first[t] is None and (out["success"][t] or out["no_more"][t]):
+                first[t] = {k: out[k][t].copy() for k in ("success", "no_more", "iterations", "n_inliers", "inlier", "s12",
+                                                          "R12", "t12", "T12", "best_inliers")}
+    tr.done()
+    for t in range(3):
+        assert first[t] is not None
+        for k, v in first[t].items():
+            assert np.array_equal(v, find[k][t], equal_nan=True), (t, k)
+    ws.close()
+
+
+@pytest.mark.parametrize("name", ["t3_mixed", "t3_small"])
+def test_visits_equal_the_reference_text(gpu, name):
+    """Six visits of 50 on the device against the same visits evaluated from the reference text
+    (tests/golden/sim3solver_ref.npz): return value, bNoMore, nInliers, mnIterations, mnBestInliers and
+    vbInliers of every visit and candidate.  The restatement shows no decision within the margin on
+    these inputs, so the counts are the text's.  In t3_mixed a second iterate after a success hits
+    again on a tie with mnBestInliers."""
+    ss = _ss()
+    case = get_case(name)
+    text = [load_iterate(name, t) for t in range(3)]
+    dev, tie = Device(case), False
+    for v in range(6):
+        out = dev.iterate(50, ss.INIT if v == 0 else 0)
+        for t in range(3):
+            got = [int(out[k][t]) for k in ("success", "no_more", "n_inliers", "iterations", "best_inliers")]
+            assert got == [int(x) for x in text[t]["visits"][v]], (v, t)
+            assert np.array_equal(out["inlier"][t], text[t]["vbInliers"][v])
+            if v > 0 and got[0] and text[t]["visits"][v - 1][0] and got[2] == text[t]["visits"][v - 1][4]:
+                tie = True
+    assert tie or name != "t3_mixed"
+
+
+def test_single_iterations_and_host_state_round_trip(gpu):
+    """n_iterations = 1 on the device, and the host entry in calls of 50 carrying its state."""
+    case = get_case("t3_mixed")
+    ss = _ss()
+    dev, tr = Device(case), Tracker(case)
+    for call in range(N_SINGLE):
+        tr.check(dev.iterate(1, ss.INIT if call == 0 else 0), 1)
+    tr.done()
+    th, state = Tracker(case), None
+    for call in range(3):
+        state = host_find(case, 50, ss.INIT if call == 0 else 0, state)
+        th.check(state, 50)
+    th.done()
+
+
+def test_stream_ordered_chain_with_a_workspace(gpu):
+    """prepare -> iterate -> active on a non-default stream with one workspace and no
+    synchronisation in between, twice back to back."""
+    import torch
+    ss = _ss()
+    case = get_case("t3_mixed")
+    good = np_good_flags(case, 9)
+    ws = ss.Workspace(3, 256, CAP)
+    st = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    outs = []
+    with torch.cuda.stream(st):
+        for _ in range(2):
+            dev = Device(case, ws=ws, good=good)
+            outs.append((dev, dev.iterate(CAP, ss.INIT)))
+    for dev, out in outs:
+        tr = Tracker(case)
+        tr.check(out, CAP, good)
+        tr.done()
+    ws.close()
+
+
+def test_malformed_samples_and_rows_stay_inside_the_buffers(gpu):
+    """Samples, cameras and counts are device data: out-of-range samples are clamped into [0, N),
+    a row whose camera is outside the rig is no inlier, a count above the capacity is clamped; the
+    run completes and the guard bytes around every output are intact."""
+    import torch
+    ss = _ss()
+    case = get_case("t1_n50")
+    bad = case["samples"].copy()
+    bad[0, :40:3, 0], bad[0, 1:40:3, 1], bad[0, 2:40:3, 2] = -7, 1 << 30, 50
+    dev = Device(case, samples=bad)
+    out = dev.iterate(CAP, ss.INIT)
+    assert ((out["hyp_inl"][0] >= -1) & (out["hyp_inl"][0] <= 50)).all()
+    dev = Device(case)
+    dev.gc.t["cam1"][0, :50:2] = 9
+    dev.gc.t["cam2"][0, 1:50:4] = -1
+    dev.gc.t["n"][0] = 1 << 20
+    torch.cuda.synchronize()
+    out = dev.iterate(CAP, ss.INIT)
+    n1 = len(case["kf1"]["kp_xy"])
+    assert out["max_its"][0] == np_max_its(n1)[0] and ((out["hyp_inl"][0] >= -1) & (out["hyp_inl"][0] <= n1)).all()
+    assert not out["success"][0] or out["inlier"][0][case["rows"][0]["idx1"][:50:2]].sum() == 0
+
+
+def test_argument_errors_of_the_device_entries(gpu):
+    import mcs_amd
+    ss = _ss()
+    case = get_case("t3_mixed")
+    dev = Device(case)
+    ran, keep = ss.new_ransac(3, dev.n1, 50)
+
+    def code(ws, n_it=50, corr=dev.corr, ran=ran, **kw):
+        a = dict(prob=PROB, min_inliers=MIN_INL, max_its_cap=CAP, flags=ss.INIT)
+        a.update(kw)
+        with pytest.raises(mcs_amd.McsError) as e:
+            ss.iterate_device(ws, corr, dev.samples, n_it, a["prob"], a["min_inliers"], a["max_its_cap"], a["flags"], ran)
+        return e.value.code
+
+    def variant(src, **kw):
+        s = type(src)()
+        ctypes.memmove(ctypes.byref(s), ctypes.byref(src), ctypes.sizeof(s))
+        for k, v in kw.items():
+            setattr(s, k, v)
+        return s
+    assert code(ss.Workspace(2, 256, CAP)) == mcs_amd.MCS_ERR_ARG           # more candidates than the workspace
+    assert code(ss.Workspace(3, 100, CAP)) == mcs_amd.MCS_ERR_ARG           # more keypoints
+    assert code(ss.Workspace(3, 256, 40)) == mcs_amd.MCS_ERR_ARG            # more iterations
+    ws = ss.Workspace(3, 256, CAP)
+    assert code(ws, n_it=0) == mcs_amd.MCS_ERR_ARG
+    assert code(ws, n_it=CAP + 1) == mcs_amd.MCS_ERR_ARG
+    assert code(ws, min_inliers=0) == mcs_amd.MCS_ERR_ARG
+    assert code(ws, prob=1.0) == mcs_amd.MCS_ERR_ARG
+    assert code(ws, flags=4) == mcs_amd.MCS_ERR_ARG
+    assert code(ws, corr=variant(dev.corr, X2=None)) == mcs_amd.MCS_ERR_ARG
+    assert code(ws, corr=variant(dev.corr, n_cams=9)) == mcs_amd.MCS_ERR_ARG
+    assert code(ws, ran=variant(ran, best_words=None)) == mcs_amd.MCS_ERR_ARG
+    with pytest.raises(mcs_amd.McsError):
+        ss.prepare_device(dev.k1, dev.p1, dev.k2, dev.p2, dev.m12, dev.ok1, dev.ok2, dev.f1, dev.f2, dev.sigma2,
+                          variant(dev.corr, cap=dev.n1 - 1))
+    tr = Tracker(case)                                                       # everything is still usable
+    dev.ws = ws
+    tr.check(dev.iterate(50, ss.INIT), 50)
