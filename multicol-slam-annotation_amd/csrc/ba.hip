@@ -15,7 +15,7 @@
 // Every reduction runs in a fixed order (no float atomics): results are bitwise
 // reproducible run to run.  The LM accept/reject decision needs two scalars per trial
 // (robust chi2, model decrease), read back by the host driver.
-#include "common.hpp"
+#include "host_util.hpp"
 #include "../../include/mcs_ba.h"
 #include "ldlt.hpp"
 #include "ba_structure.hpp"
@@ -2729,13 +2729,7 @@ void mcs_ba_default_options(mcs_ba_options* o) {
 int mcs_ba_create(int32_t device, mcs_ba_ctx** out) {
   if (!out) return MCS_ERR_ARG;
   *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("no HIP device visible (no CPU fallback)");
-    return MCS_ERR_NO_DEVICE;
-  }
-  if (device < 0 || device >= ndev) return MCS_ERR_ARG;
-  MCS_HIP_CHECK(hipSetDevice(device));
+  if (int rc = host::open_device(device, "ba_create")) return rc;
   mcs_ba_ctx* c = new (std::nothrow) mcs_ba_ctx();
   if (!c) return MCS_ERR_ARG;
   c->device = device;
@@ -3083,12 +3077,7 @@ int mcs_ba_lm_replay(int32_t device, const mcs_ba_options* o, const double* in3,
     set_error("lm_replay: null argument or n < 0");
     return MCS_ERR_ARG;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("no HIP device visible (no CPU fallback)");
-    return MCS_ERR_NO_DEVICE;
-  }
-  MCS_HIP_CHECK(hipSetDevice(device));
+  if (int rc = host::open_device(device, "lm_replay")) return rc;
   LmCtl h0;
   std::memset(&h0, 0, sizeof(h0));
   h0.tau = o->tau; h0.gain_threshold = o->gain_threshold;      // as run_device sets them
@@ -3096,29 +3085,25 @@ int mcs_ba_lm_replay(int32_t device, const mcs_ba_options* o, const double* in3,
   h0.terminate_max_iter = o->terminate_max_iter;
   h0.lin = 1; h0.ni = 2;
   h0.done = o->max_iterations <= 0 ? 1 : 0;
-  LmCtl* dc = nullptr; LmSig* ds = nullptr; double *din = nullptr, *dtr = nullptr, *dout = nullptr; int* dn = nullptr;
-  int rc = MCS_OK;
-  auto chk = [&](hipError_t e, const char* w) { if (e != hipSuccess && rc == MCS_OK) { set_hip_error(e, w, __FILE__, __LINE__); rc = MCS_ERR_HIP; } };
-  chk(hipMalloc(&dc, sizeof(LmCtl)), "malloc"); chk(hipMalloc(&ds, sizeof(LmSig)), "malloc");
-  chk(hipMalloc(&din, 3 * 8), "malloc"); chk(hipMalloc(&dtr, std::max(1, n) * 32), "malloc");
-  chk(hipMalloc(&dout, std::max(1, n) * 80), "malloc"); chk(hipMalloc(&dn, 4), "malloc");
-  if (rc == MCS_OK) {
-    chk(hipMemcpy(dc, &h0, sizeof(h0), hipMemcpyHostToDevice), "h2d");
-    chk(hipMemset(ds, 0, sizeof(LmSig)), "memset");
-    chk(hipMemcpy(din, in3, 3 * 8, hipMemcpyHostToDevice), "h2d");
-    if (n) chk(hipMemcpy(dtr, trials, (size_t)n * 32, hipMemcpyHostToDevice), "h2d");
-    chk(hipMemset(dn, 0, 4), "memset");
-    hipLaunchKernelGGL(k_lm_replay, dim3(1), dim3(64), 0, 0, dc, ds, (const double*)din, (const double*)dtr, n, dout, dn);
-    chk(hipGetLastError(), "launch");
-    chk(hipDeviceSynchronize(), "sync");
-    int32_t m = 0;
-    chk(hipMemcpy(&m, dn, 4, hipMemcpyDeviceToHost), "d2h");
-    if (rc == MCS_OK && m) chk(hipMemcpy(out, dout, (size_t)m * 80, hipMemcpyDeviceToHost), "d2h");
-    *n_out = m;
-  }
-  for (void* q : {(void*)dc, (void*)ds, (void*)din, (void*)dtr, (void*)dout, (void*)dn})
-    if (q) (void)hipFree(q);
-  return rc;
+  host::DevBufs B;
+  LmCtl* dc = B.up(&h0, 1);
+  LmSig* ds = B.alloc<LmSig>(1);
+  const double* din = B.up(in3, 3);
+  const double* dtr = B.up(trials, 4 * (size_t)n);
+  double* dout = B.alloc<double>(10 * (size_t)n);
+  int32_t* dn = B.alloc<int32_t>(1);
+  if (B.err == hipSuccess) B.err = hipMemset(ds, 0, sizeof(LmSig));
+  if (B.err == hipSuccess) B.err = hipMemset(dn, 0, 4);
+  if (B.err != hipSuccess) { set_hip_error(B.err, "lm_replay upload", __FILE__, __LINE__); return MCS_ERR_HIP; }
+  hipLaunchKernelGGL(k_lm_replay, dim3(1), dim3(64), 0, 0, dc, ds, din, dtr, n, dout, dn);
+  MCS_HIP_CHECK(hipGetLastError());
+  MCS_HIP_CHECK(hipDeviceSynchronize());
+  int32_t m = 0;
+  B.down(&m, dn, 1);
+  B.down(out, dout, 10 * (size_t)m);
+  if (B.err != hipSuccess) { set_hip_error(B.err, "lm_replay download", __FILE__, __LINE__); return MCS_ERR_HIP; }
+  *n_out = m;
+  return MCS_OK;
 }
 
 int mcs_ba_huber_eval(int32_t device, const double* e, int32_t n, double delta, double* rho0, double* rho1) {
@@ -3126,29 +3111,19 @@ int mcs_ba_huber_eval(int32_t device, const double* e, int32_t n, double delta, 
     set_error("huber_eval: null argument or n < 0");
     return MCS_ERR_ARG;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("no HIP device visible (no CPU fallback)");
-    return MCS_ERR_NO_DEVICE;
-  }
+  if (int rc = host::open_device(device, "huber_eval")) return rc;
   if (n == 0) return MCS_OK;
-  MCS_HIP_CHECK(hipSetDevice(device));
-  double *de = nullptr, *d0 = nullptr, *d1 = nullptr;
-  int rc = MCS_OK;
-  auto chk = [&](hipError_t x, const char* w) { if (x != hipSuccess && rc == MCS_OK) { set_hip_error(x, w, __FILE__, __LINE__); rc = MCS_ERR_HIP; } };
-  chk(hipMalloc(&de, (size_t)n * 8), "malloc"); chk(hipMalloc(&d0, (size_t)n * 8), "malloc");
-  chk(hipMalloc(&d1, (size_t)n * 8), "malloc");
-  if (rc == MCS_OK) {
-    chk(hipMemcpy(de, e, (size_t)n * 8, hipMemcpyHostToDevice), "h2d");
-    hipLaunchKernelGGL(k_huber_eval, dim3((n + 255) / 256), dim3(256), 0, 0, (const double*)de, n, delta,
-                       huber_dsqr(delta), d0, d1);
-    chk(hipGetLastError(), "launch");
-    chk(hipMemcpy(rho0, d0, (size_t)n * 8, hipMemcpyDeviceToHost), "d2h");
-    chk(hipMemcpy(rho1, d1, (size_t)n * 8, hipMemcpyDeviceToHost), "d2h");
-  }
-  for (void* q : {(void*)de, (void*)d0, (void*)d1})
-    if (q) (void)hipFree(q);
-  return rc;
+  host::DevBufs B;
+  const double* de = B.up(e, (size_t)n);
+  double* d0 = B.alloc<double>((size_t)n);
+  double* d1 = B.alloc<double>((size_t)n);
+  if (B.err != hipSuccess) { set_hip_error(B.err, "huber_eval upload", __FILE__, __LINE__); return MCS_ERR_HIP; }
+  hipLaunchKernelGGL(k_huber_eval, dim3((n + 255) / 256), dim3(256), 0, 0, de, n, delta, huber_dsqr(delta), d0, d1);
+  MCS_HIP_CHECK(hipGetLastError());
+  B.down(rho0, d0, (size_t)n);
+  B.down(rho1, d1, (size_t)n);
+  if (B.err != hipSuccess) { set_hip_error(B.err, "huber_eval download", __FILE__, __LINE__); return MCS_ERR_HIP; }
+  return MCS_OK;
 }
 
 int mcs_ba_point_block_eval(int32_t device, const double* H, double lambda, const double* b, const double* hpl,
@@ -3157,33 +3132,24 @@ int mcs_ba_point_block_eval(int32_t device, const double* H, double lambda, cons
     set_error("point_block_eval: null argument or n < 0");
     return MCS_ERR_ARG;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("no HIP device visible (no CPU fallback)");
-    return MCS_ERR_NO_DEVICE;
-  }
+  if (int rc = host::open_device(device, "point_block_eval")) return rc;
   if (n == 0) return MCS_OK;
-  MCS_HIP_CHECK(hipSetDevice(device));
-  double* dv = nullptr;
-  const size_t N = (size_t)n, tot = N * (9 + 3 + 18 + 9 + 3 + 18);
-  int rc = MCS_OK;
-  auto chk = [&](hipError_t x, const char* w) { if (x != hipSuccess && rc == MCS_OK) { set_hip_error(x, w, __FILE__, __LINE__); rc = MCS_ERR_HIP; } };
-  chk(hipMalloc(&dv, tot * 8), "malloc");
-  if (rc == MCS_OK) {
-    double *dH = dv, *dB = dH + 9 * N, *dP = dB + 3 * N, *dDi = dP + 18 * N, *dDb = dDi + 9 * N, *dY = dDb + 3 * N;
-    chk(hipMemcpy(dH, H, 9 * N * 8, hipMemcpyHostToDevice), "h2d");
-    chk(hipMemcpy(dB, b, 3 * N * 8, hipMemcpyHostToDevice), "h2d");
-    chk(hipMemcpy(dP, hpl, 18 * N * 8, hipMemcpyHostToDevice), "h2d");
-    if (rc == MCS_OK)
-      hipLaunchKernelGGL(k_point_block_eval, dim3((n + 255) / 256), dim3(256), 0, 0, (const double*)dH, lambda,
-                         (const double*)dB, (const double*)dP, n, dDi, dDb, dY);
-    chk(hipGetLastError(), "launch");
-    chk(hipMemcpy(Dinv, dDi, 9 * N * 8, hipMemcpyDeviceToHost), "d2h");
-    chk(hipMemcpy(db, dDb, 3 * N * 8, hipMemcpyDeviceToHost), "d2h");
-    chk(hipMemcpy(Y, dY, 18 * N * 8, hipMemcpyDeviceToHost), "d2h");
-  }
-  if (dv) (void)hipFree(dv);
-  return rc;
+  const size_t N = (size_t)n;
+  host::DevBufs B;
+  const double* dH = B.up(H, 9 * N);
+  const double* dB = B.up(b, 3 * N);
+  const double* dP = B.up(hpl, 18 * N);
+  double* dDi = B.alloc<double>(9 * N);
+  double* dDb = B.alloc<double>(3 * N);
+  double* dY = B.alloc<double>(18 * N);
+  if (B.err != hipSuccess) { set_hip_error(B.err, "point_block_eval upload", __FILE__, __LINE__); return MCS_ERR_HIP; }
+  hipLaunchKernelGGL(k_point_block_eval, dim3((n + 255) / 256), dim3(256), 0, 0, dH, lambda, dB, dP, n, dDi, dDb, dY);
+  MCS_HIP_CHECK(hipGetLastError());
+  B.down(Dinv, dDi, 9 * N);
+  B.down(db, dDb, 3 * N);
+  B.down(Y, dY, 18 * N);
+  if (B.err != hipSuccess) { set_hip_error(B.err, "point_block_eval download", __FILE__, __LINE__); return MCS_ERR_HIP; }
+  return MCS_OK;
 }
 
 int mcs_ldlt_set_wait_ticks(int64_t ticks) {
@@ -3199,12 +3165,7 @@ int mcs_dense_ldlt_solve(int32_t device, const double* S, int32_t n, const doubl
 int mcs_dense_ldlt_solve_ex(int32_t device, const double* S, int32_t n, const double* b, double* x,
                             int32_t* zero_pivot, int32_t path) {
   if (!S || !b || !x || n < 1 || path < 0 || path > 3) return MCS_ERR_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("no HIP device visible (no CPU fallback)");
-    return MCS_ERR_NO_DEVICE;
-  }
-  MCS_HIP_CHECK(hipSetDevice(device));
+  if (int rc = host::open_device(device, "dense_ldlt_solve")) return rc;
   const int T = ldlt::tiles_for(n);
   const size_t NT = ldlt::tile_doubles(T), Np = (size_t)ldlt::TB * T;
   // path 0: the tile band of S (the widest tile diagonal holding a non-zero), as the BA derives
@@ -3223,18 +3184,17 @@ int mcs_dense_ldlt_solve_ex(int32_t device, const double* S, int32_t n, const do
   for (int r = 0; r < n; r++)
     for (int c = 0; c <= r; c++) hA[ldlt::sidx(r, c, T)] = S[(size_t)r * n + c];
   for (int r = 0; r < n; r++) hb[r] = b[r];
-  double *dA = nullptr, *db = nullptr, *dx = nullptr, *dL = nullptr, *dI = nullptr, *dz = nullptr;
-  int* dflag = nullptr;
+  host::DevBufs B;
+  double *dA = B.alloc<double>(NT), *dL = B.alloc<double>(NT), *dI = B.alloc<double>((size_t)T * 4096);
+  double *db = B.alloc<double>(Np), *dx = B.alloc<double>(Np), *dz = B.alloc<double>(Np);
+  int* dflag = B.alloc<int>(4);
   hipStream_t st = nullptr;
   int rc = MCS_OK;
   auto chk = [&](hipError_t e, const char* what) {
     if (e != hipSuccess && rc == MCS_OK) { set_hip_error(e, what, __FILE__, __LINE__); rc = MCS_ERR_HIP; }
   };
+  chk(B.err, "malloc");
   chk(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "stream");
-  chk(hipMalloc(&dA, NT * 8), "malloc"); chk(hipMalloc(&dL, NT * 8), "malloc");
-  chk(hipMalloc(&dI, (size_t)T * 4096 * 8), "malloc");
-  chk(hipMalloc(&db, Np * 8), "malloc"); chk(hipMalloc(&dx, Np * 8), "malloc"); chk(hipMalloc(&dz, Np * 8), "malloc");
-  chk(hipMalloc(&dflag, 16), "malloc");
   if (rc == MCS_OK) {
     chk(hipMemcpyAsync(dA, hA.data(), NT * 8, hipMemcpyHostToDevice, st), "h2d");
     chk(hipMemcpyAsync(db, hb.data(), Np * 8, hipMemcpyHostToDevice, st), "h2d");
@@ -3266,9 +3226,7 @@ int mcs_dense_ldlt_solve_ex(int32_t device, const double* S, int32_t n, const do
     }
     if (zero_pivot) *zero_pivot = fl & ldlt::kFlagZeroPivot;
   }
-  for (void* q : {(void*)dA, (void*)dL, (void*)dI, (void*)db, (void*)dx, (void*)dz, (void*)dflag})
-    if (q) (void)hipFree(q);
-  if (st) (void)hipStreamDestroy(st);
+  if (st) (void)hipStreamDestroy(st);   // the buffers go with B
   return rc;
 }
 

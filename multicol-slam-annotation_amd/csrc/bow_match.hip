@@ -5,7 +5,7 @@
 //            SearchByBoW(cMultiKeyFrame*, cMultiKeyFrame*, ...)   src/cORBmatcher.cpp:885-966
 //            ComputeThreeMaxima                                   src/cORBmatcher.cpp:2399-2441
 //            TemplatedVocabulary::transform (FeatureVector part)  TemplatedVocabulary.h:1126-1196
-#include "common.hpp"
+#include "host_util.hpp"
 #include "ham_dist.hpp"
 #include "../../include/mcs_matcher.h"
 #include <cstring>
@@ -426,14 +426,6 @@ static int bow_ws_create(int32_t device, int32_t max_kp, int32_t max_candidates,
 
 namespace mcs {
 
-static int bow_check_bytes(int bytes) {
-  if (bytes != 16 && bytes != 32 && bytes != 64) {
-    set_error("SearchByBoW: descriptor bytes must be 16, 32 or 64");
-    return MCS_ERR_ARG;
-  }
-  return MCS_OK;
-}
-
 // What can be checked without reading a set's arrays (device and host entries alike).
 static int bow_check_shape(const mcs_bow_set* s, const char* what, bool one_frame, bool need_has,
                            bool need_angle, bool need_fv) {
@@ -485,15 +477,6 @@ static int bow_check_host(const mcs_bow_set* s, const char* what, bool need_fv) 
       if (feat[i] >= (uint32_t)n) return fail("feature index >= n_kp", k);
   }
   return MCS_OK;
-}
-
-static int bow_no_device() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("no HIP device visible (no CPU fallback)");
-    return 0;
-  }
-  return ndev;
 }
 
 #define MCS_BOW_DISPATCH(bytes, masked, LAUNCH)                         \
@@ -555,68 +538,52 @@ static hipError_t bow_run_b(mcs_bow_workspace* ws, const mcs_bow_set& a, const m
   return hipGetLastError();
 }
 
-// Device copy of a host set (the arrays a run reads); buffers are appended to `bufs`.
-static hipError_t bow_upload(const mcs_bow_set& h, int bytes, bool with_fv, bool with_angle, bool with_has,
-                             mcs_bow_set* d, std::vector<void*>& bufs) {
+// Device copy of a host set (the arrays a run reads).
+static void bow_upload(host::DevBufs& B, const mcs_bow_set& h, int bytes, bool with_fv, bool with_angle,
+                       bool with_has, mcs_bow_set* d) {
   *d = h;
-  hipError_t e = hipSuccess;
-  auto up = [&](const void* src, size_t n) -> void* {
-    if (e != hipSuccess || !src) return nullptr;
-    void* p = nullptr;
-    e = hipMalloc(&p, std::max<size_t>(n, 16));
-    if (e != hipSuccess) return nullptr;
-    bufs.push_back(p);
-    if (n) e = hipMemcpy(p, src, n, hipMemcpyHostToDevice);
-    return p;
-  };
   const size_t n = (size_t)h.n_kp_total, nf = (size_t)h.n_frames;
-  d->off = (const int32_t*)up(h.off, 4 * (nf + 1));
-  d->desc = (const uint8_t*)up(h.desc, n * bytes);
-  d->mask = (const uint8_t*)up(h.mask, n * bytes);
-  d->angle = with_angle ? (const float*)up(h.angle, 4 * n) : nullptr;
-  d->has_mp = with_has ? (const uint8_t*)up(h.has_mp, n) : nullptr;
-  d->fv_node = with_fv ? (const uint32_t*)up(h.fv_node, 4 * n) : nullptr;
-  d->fv_ptr = with_fv ? (const int32_t*)up(h.fv_ptr, 4 * (n + nf)) : nullptr;
-  d->fv_feat = with_fv ? (const uint32_t*)up(h.fv_feat, 4 * n) : nullptr;
-  d->fv_n = with_fv ? (const int32_t*)up(h.fv_n, 4 * nf) : nullptr;
-  return e;
+  d->off = B.up(h.off, nf + 1);
+  d->desc = B.up(h.desc, n * bytes);
+  d->mask = B.up(h.mask, n * bytes);
+  d->angle = with_angle ? B.up(h.angle, n) : nullptr;
+  d->has_mp = with_has ? B.up(h.has_mp, n) : nullptr;
+  d->fv_node = with_fv ? B.up(h.fv_node, n) : nullptr;
+  d->fv_ptr = with_fv ? B.up(h.fv_ptr, n + nf) : nullptr;
+  d->fv_feat = with_fv ? B.up(h.fv_feat, n) : nullptr;
+  d->fv_n = with_fv ? B.up(h.fv_n, nf) : nullptr;
 }
 
 // Shared body of the two host entries: upload, run on a workspace of the call's size, download.
 static int bow_host_run(bool overload_b, int device, const mcs_bow_set* one, const mcs_bow_set* many, int bytes,
                         int th_low, double nnratio, int check_ori, int32_t* out, int32_t* n_matches) {
   const int n_one = one->n_kp_total, n_kf = many->n_frames;
-  for (int64_t i = 0; i < (int64_t)n_kf * n_one; i++) out[i] = -1;
-  for (int k = 0; k < n_kf; k++) n_matches[k] = 0;
+  auto reset = [&] {
+    for (int64_t i = 0; i < (int64_t)n_kf * n_one; i++) out[i] = -1;
+    for (int k = 0; k < n_kf; k++) n_matches[k] = 0;
+  };
+  reset();
   if (n_kf == 0 || n_one == 0 || many->n_kp_total == 0) return MCS_OK;
-  const int ndev = bow_no_device();
-  if (!ndev) return MCS_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev) { set_error("bad device ordinal"); return MCS_ERR_ARG; }
   mcs_bow_workspace* ws = nullptr;
   int max_kp = n_one;
   for (int k = 0; k < n_kf; k++) max_kp = std::max(max_kp, many->off[k + 1] - many->off[k]);
-  int rc = bow_ws_create(device, max_kp, n_kf, overload_b, &ws);
+  int rc = bow_ws_create(device, max_kp, n_kf, overload_b, &ws);   // opens the device
   if (rc != MCS_OK) return rc;
-  std::vector<void*> bufs;
+  host::DevBufs B;
   mcs_bow_set d_one, d_many;
-  hipError_t e = bow_upload(*one, bytes, !overload_b, check_ori != 0, overload_b, &d_one, bufs);
-  if (e == hipSuccess) e = bow_upload(*many, bytes, !overload_b, check_ori != 0, true, &d_many, bufs);
-  int32_t *d_out = nullptr, *d_n = nullptr;
-  if (e == hipSuccess) e = hipMalloc((void**)&d_out, 4 * (size_t)n_kf * n_one);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_n, 4 * (size_t)n_kf);
-  if (e == hipSuccess)
-    e = overload_b ? bow_run_b(ws, d_one, d_many, bytes, th_low, nnratio, d_out, d_n, nullptr)
-                   : bow_run_a(ws, d_one, d_many, bytes, th_low, nnratio, check_ori, d_out, d_n, nullptr);
-  if (e == hipSuccess) e = hipMemcpy(out, d_out, 4 * (size_t)n_kf * n_one, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(n_matches, d_n, 4 * (size_t)n_kf, hipMemcpyDeviceToHost);
-  for (void* p : bufs) (void)hipFree(p);
-  if (d_out) (void)hipFree(d_out);
-  if (d_n) (void)hipFree(d_n);
+  bow_upload(B, *one, bytes, !overload_b, check_ori != 0, overload_b, &d_one);
+  bow_upload(B, *many, bytes, !overload_b, check_ori != 0, true, &d_many);
+  int32_t* d_out = B.alloc<int32_t>((size_t)n_kf * n_one);
+  int32_t* d_n = B.alloc<int32_t>((size_t)n_kf);
+  if (B.err == hipSuccess)
+    B.err = overload_b ? bow_run_b(ws, d_one, d_many, bytes, th_low, nnratio, d_out, d_n, nullptr)
+                       : bow_run_a(ws, d_one, d_many, bytes, th_low, nnratio, check_ori, d_out, d_n, nullptr);
+  B.down(out, d_out, (size_t)n_kf * n_one);
+  B.down(n_matches, d_n, (size_t)n_kf);
   mcs_bow_workspace_destroy(ws);
-  if (e != hipSuccess) {
-    for (int64_t i = 0; i < (int64_t)n_kf * n_one; i++) out[i] = -1;
-    for (int k = 0; k < n_kf; k++) n_matches[k] = 0;
-    set_hip_error(e, "SearchByBoW", __FILE__, __LINE__);
+  if (B.err != hipSuccess) {
+    reset();
+    set_hip_error(B.err, "SearchByBoW", __FILE__, __LINE__);
     return MCS_ERR_HIP;
   }
   return MCS_OK;
@@ -625,7 +592,7 @@ static int bow_host_run(bool overload_b, int device, const mcs_bow_set* one, con
 // Argument checks common to the four search entries.
 static int bow_check_call(const mcs_bow_set* one, const mcs_bow_set* many, int bytes, bool overload_b,
                           int check_ori, const void* out, const void* n_matches) {
-  int rc = bow_check_bytes(bytes);
+  int rc = host::check_desc_bytes(bytes, "SearchByBoW");
   if (rc) return rc;
   const char* n1 = overload_b ? "kf1" : "f";
   const char* n2 = overload_b ? "kf2s" : "kfs";
@@ -664,10 +631,7 @@ static int bow_ws_create(int32_t device, int32_t max_kp, int32_t max_candidates,
     return MCS_ERR_ARG;
   }
   *out = nullptr;
-  const int ndev = bow_no_device();
-  if (!ndev) return MCS_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev) { set_error("bad device ordinal"); return MCS_ERR_ARG; }
-  MCS_HIP_CHECK(hipSetDevice(device));
+  if (int rc = host::open_device(device, "bow workspace")) return rc;
   auto* w = new (std::nothrow) mcs_bow_workspace();
   if (!w) return MCS_ERR_ARG;
   w->device = device; w->max_kp = max_kp; w->max_cand = max_candidates;

@@ -11,7 +11,7 @@
 //   computeOrientation / IC_Angle          :221-248     -> k_orient_desc (part 1)
 //   boxFilter 5x5                          :1301        -> k_pyr_rows (fused)
 //   compute_ORB / rotatePattern            :285-354     -> k_orient_desc (part 2)
-#include "common.hpp"
+#include "host_util.hpp"
 #include "extractor_plan.hpp"
 #include "extractor_kernels.hpp"
 #include "pyr_units.hpp"
@@ -297,13 +297,7 @@ int mcs_extractor_create(const mcs_extractor_params* p, int32_t width, int32_t h
                          int32_t max_frames, int32_t device, mcs_extractor** out) {
   if (!p || !out || max_frames < 1) { set_error("null argument"); return MCS_ERR_ARG; }
   *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("no HIP device visible (libmcs_amd has no CPU fallback)");
-    return MCS_ERR_NO_DEVICE;
-  }
-  if (device < 0 || device >= ndev) { set_error("bad device ordinal"); return MCS_ERR_ARG; }
-  MCS_HIP_CHECK(hipSetDevice(device));
+  if (int rc = host::open_device(device, "extractor")) return rc;
   mcs_extractor* h = new (std::nothrow) mcs_extractor();
   if (!h) return MCS_ERR_ARG;
   int rc = build_plan(*p, width, height, h->plan);

@@ -88,10 +88,7 @@ __global__ __launch_bounds__(256) void k_in_frustum(const double* __restrict__ p
   const double* P = pts + 3 * (int64_t)p;
   double u, v;
   world_to_cam_img(R, t, camv + 17 * c, P, u, v);
-  // isPointInMirrorMask(u, v, 0): cvRound, bounds (> 0 and < size), mask > 0
-  const int ur = (int)rint(u), vr = (int)rint(v);
-  if (ur >= mw || ur <= 0 || vr >= mh || vr <= 0) return;
-  if (masks[(int64_t)c * mw * mh + (int64_t)vr * mw + ur] == 0) return;
+  if (!in_mirror_mask(masks, c, mw, mh, u, v)) return;
   // distance to the camera centre (Get_MtMc translation) inside the invariance region
   const double maxD = __dmul_rn(1.2, dist[2 * (int64_t)p + 1]);
   const double minD = __dmul_rn(0.8, dist[2 * (int64_t)p]);
@@ -102,11 +99,7 @@ __global__ __launch_bounds__(256) void k_in_frustum(const double* __restrict__ p
   const double* Pn = nrm + 3 * (int64_t)p;
   const double vc = __ddiv_rn(__dadd_rn(__dadd_rn(__dmul_rn(PO[0], Pn[0]), __dmul_rn(PO[1], Pn[1])),
                                         __dmul_rn(PO[2], Pn[2])), d);
-  // nPredictedLevel = lower_bound(mvScaleFactors, dist / minDistance), capped
-  const double ratio = __ddiv_rn(d, minD);
-  int lv = 0;
-  while (lv < L && scale[lv] < ratio) lv++;
-  if (lv >= L) lv = L - 1;
+  const int lv = predict_level(scale, L, __ddiv_rn(d, minD));
   in_view[q] = 1;
   proj[2 * q] = u;
   proj[2 * q + 1] = v;

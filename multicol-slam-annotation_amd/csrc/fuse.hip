@@ -15,6 +15,7 @@
 // GetFeaturesInArea, best Hamming distance.  The state-dependent tails (:1379-1415, :1536-1563,
 // :1692-1715) are mcs_fuse_select (fuse_select.cpp) on the host.
 // Compiled with -ffp-contract=off; every rounding follows the reference's expression order.
+#include "host_util.hpp"
 #include "proj_window.hpp"
 #include <algorithm>
 #include <climits>
@@ -100,10 +101,7 @@ __device__ __forceinline__ bool project(const Args& a, int t, int i, int c, doub
   const double* Rt = a.Rt + 12 * ((int64_t)t * a.C + c);
   const double* P = a.q_pos + 3 * (int64_t)i;
   frm::world_to_cam_img(Rt, Rt + 9, a.cam + 17 * c, P, *u, *v);
-  // isPointInMirrorMask(u, v, 0): cvRound, bounds (> 0 and < size), mask > 0
-  const int ur = (int)rint(*u), vr = (int)rint(*v);
-  if (ur >= a.mw || ur <= 0 || vr >= a.mh || vr <= 0) return false;
-  if (a.mirror[(int64_t)c * a.mw * a.mh + (int64_t)vr * a.mw + ur] == 0) return false;
+  if (!frm::in_mirror_mask(a.mirror, c, a.mw, a.mh, *u, *v)) return false;
   const double maxD = __dmul_rn(1.2, a.q_dist[2 * (int64_t)i + 1]);
   const double minD = __dmul_rn(0.8, a.q_dist[2 * (int64_t)i]);
   const double* Mt = a.m_t + 16 * (int64_t)t;   // Ow = Hom2T(M_t)
@@ -112,10 +110,7 @@ __device__ __forceinline__ bool project(const Args& a, int t, int i, int c, doub
                                   __dmul_rn(PO[2], PO[2])));
   if (a.rule != 2) d = (double)(float)d;   // `const float dist3D` (:1306, :1464); double at :1623
   if (d < minD || d > maxD) return false;
-  const double ratio = __ddiv_rn(d, minD);
-  int lv = 0;
-  while (lv < a.L && a.scale[lv] < ratio) lv++;
-  if (lv >= a.L) lv = a.L - 1;
+  const int lv = frm::predict_level(a.scale, a.L, __ddiv_rn(d, minD));
   *level = lv;
   *radius = __dmul_rn(a.th, a.scale[lv]);
   return true;
@@ -164,28 +159,10 @@ __global__ __launch_bounds__(256) void k_fuse(Args a) {
   }
 }
 
-// device allocations of one host-buffer call, released on every return path
-struct DevBufs {
-  std::vector<void*> p;
-  hipError_t err = hipSuccess;
-  template <class T> T* alloc(size_t n) {
-    void* q = nullptr;
-    if (err == hipSuccess) err = hipMalloc(&q, std::max<size_t>(1, n) * sizeof(T));
-    if (q) p.push_back(q);
-    return static_cast<T*>(q);
-  }
-  template <class T> T* up(const T* h, size_t n) {
-    T* d = alloc<T>(n);
-    if (err == hipSuccess && h && n) err = hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice);
-    return d;
-  }
-  ~DevBufs() { for (void* q : p) (void)hipFree(q); }
-};
-
 static int check_args(int rule, const mcs_fuse_targets* tg, const mcs_fuse_queries* q) {
   if (!tg || !q) { set_error("fuse: null targets / queries"); return MCS_ERR_ARG; }
   if (rule < 0 || rule > 2) { set_error("fuse: rule must be 0, 1 or 2"); return MCS_ERR_ARG; }
-  if (tg->bytes != 16 && tg->bytes != 32 && tg->bytes != 64) { set_error("fuse: bytes must be 16, 32 or 64"); return MCS_ERR_ARG; }
+  if (int rc = host::check_desc_bytes(tg->bytes, "fuse")) return rc;
   if (tg->n_cams < 1 || tg->n_cams > kMaxCams) { set_error("fuse: 1 to 8 cameras"); return MCS_ERR_ARG; }
   if (tg->n_targets < 0 || tg->n_kp_total < 0 || q->nq < 0 || tg->n_levels < 1 || tg->mirror_w < 1 || tg->mirror_h < 1) {
     set_error("fuse: negative count or empty pyramid / mirror mask");
@@ -219,13 +196,7 @@ extern "C" {
 
 int mcs_fuse_workspace_create(int32_t device, int32_t max_targets, mcs_fuse_workspace** out) {
   if (!out || max_targets < 1) { set_error("fuse workspace: bad argument"); return MCS_ERR_ARG; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("no HIP device visible (no CPU fallback)");
-    return MCS_ERR_NO_DEVICE;
-  }
-  if (device < 0 || device >= ndev) { set_error("fuse workspace: no such device"); return MCS_ERR_ARG; }
-  MCS_HIP_CHECK(hipSetDevice(device));
+  if (int rc = host::open_device(device, "fuse workspace")) return rc;
   mcs_fuse_workspace* w = new mcs_fuse_workspace;
   w->device = device;
   w->max_targets = max_targets;
@@ -302,71 +273,37 @@ int mcs_fuse(int32_t device, int32_t rule, int32_t flags, const mcs_fuse_targets
              int32_t* best_kp, int32_t* best_dist, uint8_t* epi_ok) {
   int rc = fuse::check_args(rule, tg, q);
   if (rc) return rc;
-  const int T = tg->n_targets, C = tg->n_cams, nq = q->nq;
-  const size_t nw = (size_t)T * nq * C;
+  const int T = tg->n_targets, nq = q->nq;
+  const size_t nw = (size_t)T * nq * tg->n_cams;
   if (nw == 0) return MCS_OK;
   if (!best_kp || !best_dist || (rule == 0 && !epi_ok) || (tg->n_kp_total > 0 && !tg->kp_cam)) {
     set_error("fuse: null host buffer");
     return MCS_ERR_ARG;
   }
-  if (tg->off[0] != 0 || tg->off[T] != tg->n_kp_total) { set_error("fuse: off[0] must be 0 and off[n_targets] n_kp_total"); return MCS_ERR_ARG; }
-  for (int t = 0; t < T; t++) {
-    if (tg->off[t + 1] < tg->off[t]) { set_error("fuse: offsets must be non-decreasing"); return MCS_ERR_ARG; }
-    if (tg->off[t + 1] - tg->off[t] >= fuse::kMaxKpPerTarget) {
-      set_error("fuse: keypoints per target must be below 2^19 (position field of the key)");
-      return MCS_ERR_ARG;
-    }
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("no HIP device visible (no CPU fallback)");
-    return MCS_ERR_NO_DEVICE;
-  }
-  if (device < 0 || device >= ndev) { set_error("fuse: no such device"); return MCS_ERR_ARG; }
-  MCS_HIP_CHECK(hipSetDevice(device));
-  const size_t ncell = (size_t)C * win::kCols * win::kRows, nk = (size_t)tg->n_kp_total, nb = (size_t)tg->bytes;
-  std::vector<int32_t> cell_ptr((size_t)T * (ncell + 1)), cell_kp(std::max<size_t>(1, nk), 0);
-  for (int t = 0; t < T; t++) {
-    const size_t o = (size_t)tg->off[t];
-    rc = mcs_frame_grid_build(tg->kp_xy ? tg->kp_xy + 2 * o : nullptr, tg->kp_cam ? tg->kp_cam + o : nullptr,
-                              tg->off[t + 1] - tg->off[t], C, tg->grid_params,
-                              cell_ptr.data() + (size_t)t * (ncell + 1), cell_kp.data() + o, nullptr);
-    if (rc) { set_error("fuse: grid build failed"); return rc; }
-  }
-  fuse::DevBufs B;
-  mcs_fuse_targets d = *tg;
-  d.off = B.up(tg->off, (size_t)T + 1);
-  d.kp_xy = B.up(tg->kp_xy, 2 * nk);
-  d.kp_octave = B.up(tg->kp_octave, nk);
-  d.kp_cam = nullptr;
-  d.desc = B.up(tg->desc, nk * nb);
-  d.mask = tg->mask ? B.up(tg->mask, nk * nb) : nullptr;
-  d.rays = rule == 0 ? B.up(tg->rays, 3 * nk) : nullptr;
-  d.m_t = B.up(tg->m_t, 16 * (size_t)T);
-  d.m_c = B.up(tg->m_c, 16 * (size_t)C);
-  d.cam = B.up(tg->cam, 17 * (size_t)C);
-  d.mirror = B.up(tg->mirror, (size_t)C * tg->mirror_w * tg->mirror_h);
-  d.grid_params = B.up(tg->grid_params, 4 * (size_t)C);
-  d.scale = B.up(tg->scale, (size_t)tg->n_levels);
-  d.cell_ptr = B.up(cell_ptr.data(), cell_ptr.size());
-  d.cell_kp = B.up(cell_kp.data(), cell_kp.size());
+  if ((rc = host::check_set_offsets(tg->off, T, tg->n_kp_total, fuse::kMaxKpPerTarget, "fuse"))) return rc;
+  if ((rc = host::open_device(device, "fuse"))) return rc;
+  const size_t nb = (size_t)tg->bytes;
+  host::DevBufs B;
+  mcs_fuse_targets d;
+  if ((rc = host::upload_kf_set(B, *tg, host::kKfSearch | (rule == 0 ? host::kKfRays : 0), &d))) return rc;
   mcs_fuse_queries dq = *q;
   dq.pos = B.up(q->pos, 3 * (size_t)nq);
   dq.dist = B.up(q->dist, 2 * (size_t)nq);
   dq.desc = B.up(q->desc, (size_t)nq * nb);
-  dq.mask = q->mask ? B.up(q->mask, (size_t)nq * nb) : nullptr;
+  dq.mask = B.up(q->mask, (size_t)nq * nb);
   dq.rays = rule == 0 ? B.up(q->rays, 3 * (size_t)nq) : nullptr;
   dq.m_t = rule == 0 ? B.up(q->m_t, 16) : nullptr;
-  const uint8_t* d_skip = q_skip ? B.up(q_skip, (size_t)T * nq) : nullptr;
+  const uint8_t* d_skip = B.up(q_skip, (size_t)T * nq);
   int32_t* d_bk = B.alloc<int32_t>(nw);
   int32_t* d_bd = B.alloc<int32_t>(nw);
   uint8_t* d_ep = rule == 0 ? B.alloc<uint8_t>(nw) : nullptr;
   if (B.err != hipSuccess) { set_hip_error(B.err, "fuse upload", __FILE__, __LINE__); return MCS_ERR_HIP; }
   rc = mcs_fuse_device(nullptr, rule, flags, &d, &dq, th, th_low, d_skip, d_bk, d_bd, d_ep, nullptr);
   if (rc) return rc;
-  MCS_HIP_CHECK(hipMemcpy(best_kp, d_bk, 4 * nw, hipMemcpyDeviceToHost));
-  MCS_HIP_CHECK(hipMemcpy(best_dist, d_bd, 4 * nw, hipMemcpyDeviceToHost));
-  if (rule == 0) MCS_HIP_CHECK(hipMemcpy(epi_ok, d_ep, nw, hipMemcpyDeviceToHost));
+  B.down(best_kp, d_bk, nw);
+  B.down(best_dist, d_bd, nw);
+  if (rule == 0) B.down(epi_ok, d_ep, nw);
+  if (B.err != hipSuccess) { set_hip_error(B.err, "fuse download", __FILE__, __LINE__); return MCS_ERR_HIP; }
   return MCS_OK;
 }
 

@@ -4,7 +4,7 @@
 // Reference: DescriptorDistance64 / ...Masked   src/cORBmatcher.cpp:2443-2477
 //            SearchForTriangulationRaw          src/cORBmatcher.cpp:968-1156
 //            best/second-best scans             src/cORBmatcher.cpp:67-163, 326-475
-#include "common.hpp"
+#include "host_util.hpp"
 #include "proj_window.hpp"
 #include "ham_dist.hpp"
 #include "top2_net.hpp"
@@ -384,13 +384,7 @@ __global__ __launch_bounds__(kHamThreads) void k_dense(const uint8_t* __restrict
   for (int j = 0; j < nt_tile; j++) D[(int64_t)qi * nb + t0 + j] = (uint16_t)ham_dist_v<W>(q, &tile[j * (W / 4)]);
 }
 
-static int check_bytes(int bytes) {
-  if (bytes != 16 && bytes != 32 && bytes != 64) {
-    set_error("descriptor bytes must be 16, 32 or 64");
-    return MCS_ERR_ARG;
-  }
-  return MCS_OK;
-}
+static int check_bytes(int bytes) { return host::check_desc_bytes(bytes, "matcher"); }
 
 #define MCS_DISPATCH_W(bytes, KERNEL, ...)                                                  \
   do {                                                                                     \
@@ -1088,45 +1082,26 @@ static int search_for_triangulation(const uint8_t* desc1, const uint8_t* mask1,
   for (int i = 0; i < n2; i++)
     if (cam2[i] < 0 || cam2[i] >= ncams) { set_error("triangulation: cam2 out of range"); return MCS_ERR_ARG; }
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("no HIP device visible (no CPU fallback)");
-    return MCS_ERR_NO_DEVICE;
-  }
+  if ((rc = host::have_device(&ndev))) return rc;
   // host entry: upload, run the device search, download (one synchronisation)
-  uint8_t *dA = nullptr, *dB = nullptr, *dmA = nullptr, *dmB = nullptr, *dhA = nullptr,
-          *dhB = nullptr;
-  int32_t *dcA = nullptr, *dcB = nullptr, *dm12 = nullptr, *dn = nullptr;
-  double *drA = nullptr, *drB = nullptr, *dE = nullptr;
-  hipError_t e = hipSuccess;
-  auto chk = [&](hipError_t x) { if (e == hipSuccess) e = x; };
-  chk(hipMalloc((void**)&dA, (size_t)n1 * bytes));
-  chk(hipMalloc((void**)&dB, (size_t)n2 * bytes));
-  if (masked) {
-    chk(hipMalloc((void**)&dmA, (size_t)n1 * bytes));
-    chk(hipMalloc((void**)&dmB, (size_t)n2 * bytes));
-    chk(hipMemcpy(dmA, mask1, (size_t)n1 * bytes, hipMemcpyHostToDevice));
-    chk(hipMemcpy(dmB, mask2, (size_t)n2 * bytes, hipMemcpyHostToDevice));
-  }
-  chk(hipMalloc((void**)&dhA, n1));
-  chk(hipMalloc((void**)&dhB, n2));
-  chk(hipMalloc((void**)&dcA, 4 * (size_t)n1));
-  chk(hipMalloc((void**)&dcB, 4 * (size_t)n2));
-  chk(hipMalloc((void**)&drA, 24 * (size_t)n1));
-  chk(hipMalloc((void**)&drB, 24 * (size_t)n2));
-  chk(hipMalloc((void**)&dE, 72 * (size_t)ncams * ncams));
-  chk(hipMalloc((void**)&dm12, 4 * (size_t)n1));
-  chk(hipMalloc((void**)&dn, 4));
-  chk(hipMemcpy(dA, desc1, (size_t)n1 * bytes, hipMemcpyHostToDevice));
-  chk(hipMemcpy(dB, desc2, (size_t)n2 * bytes, hipMemcpyHostToDevice));
-  chk(hipMemcpy(dhA, has_mp1, n1, hipMemcpyHostToDevice));
-  chk(hipMemcpy(dhB, has_mp2, n2, hipMemcpyHostToDevice));
-  chk(hipMemcpy(dcA, cam1, 4 * (size_t)n1, hipMemcpyHostToDevice));
-  chk(hipMemcpy(dcB, cam2, 4 * (size_t)n2, hipMemcpyHostToDevice));
-  chk(hipMemcpy(drA, rays1, 24 * (size_t)n1, hipMemcpyHostToDevice));
-  chk(hipMemcpy(drB, rays2, 24 * (size_t)n2, hipMemcpyHostToDevice));
-  chk(hipMemcpy(dE, E, 72 * (size_t)ncams * ncams, hipMemcpyHostToDevice));
+  host::DevBufs B;
+  const size_t s1 = (size_t)n1, s2 = (size_t)n2;
+  const uint8_t* dA = B.up(desc1, s1 * bytes);
+  const uint8_t* dB = B.up(desc2, s2 * bytes);
+  const uint8_t* dmA = B.up(mask1, s1 * bytes);
+  const uint8_t* dmB = B.up(mask2, s2 * bytes);
+  const uint8_t* dhA = B.up(has_mp1, s1);
+  const uint8_t* dhB = B.up(has_mp2, s2);
+  const int32_t* dcA = B.up(cam1, s1);
+  const int32_t* dcB = B.up(cam2, s2);
+  const double* drA = B.up(rays1, 3 * s1);
+  const double* drB = B.up(rays2, 3 * s2);
+  const double* dE = B.up(E, 9 * (size_t)ncams * ncams);
+  int32_t* dm12 = B.alloc<int32_t>(s1);
+  int32_t* dn = B.alloc<int32_t>(1);
+  hipError_t& e = B.err;
   int dev = 0;
-  chk(hipGetDevice(&dev));
+  if (e == hipSuccess) e = hipGetDevice(&dev);
   {
     // one workspace per device, kept for the process and grown on demand (a call holds the
     // lock for its whole run: calls on one device share the buffers)
@@ -1142,12 +1117,9 @@ static int search_for_triangulation(const uint8_t* desc1, const uint8_t* mask1,
     if (e == hipSuccess)
       e = tri_run(ws, dA, dmA, dcA, dhA, drA, n1, dB, dmB, dcB, dhB, drB, n2, ncams, dE, bytes, th_low,
                   epi_thresh, dm12, dn, nullptr);
-    chk(hipMemcpy(matches12, dm12, 4 * (size_t)n1, hipMemcpyDeviceToHost));
-    chk(hipMemcpy(n_matches, dn, 4, hipMemcpyDeviceToHost));
+    B.down(matches12, dm12, s1);
+    B.down(n_matches, dn, 1);
   }
-  void* bufs[] = {dA, dB, dmA, dmB, dhA, dhB, dcA, dcB, drA, drB, dE, dm12, dn};
-  for (void* p : bufs)
-    if (p) (void)hipFree(p);
   if (e != hipSuccess) {
     for (int i = 0; i < n1; i++) matches12[i] = -1;
     *n_matches = 0;
@@ -1194,10 +1166,7 @@ int mcs_tri_workspace_create(int32_t device, int32_t max_n1, int32_t max_n2, mcs
     return MCS_ERR_ARG;
   }
   *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device visible (no CPU fallback)"); return MCS_ERR_NO_DEVICE; }
-  if (device < 0 || device >= ndev) { set_error("bad device ordinal"); return MCS_ERR_ARG; }
-  MCS_HIP_CHECK(hipSetDevice(device));
+  if (int rc = host::open_device(device, "tri workspace")) return rc;
   auto* w = new (std::nothrow) mcs_tri_workspace();
   if (!w) return MCS_ERR_ARG;
   w->device = device; w->max_n1 = max_n1; w->max_n2 = max_n2;

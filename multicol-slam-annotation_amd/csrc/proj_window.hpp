@@ -1,5 +1,7 @@
-// Device functions shared by frame.hip, window.hip, hamming.hip, fuse.hip and sim3_match.hip: the
-// omni projection (cayley2rot, M_t M_c, WorldToCamHom_fast / WorldToImg, ImgToWorld), the window
+// Device functions shared by frame.hip, window.hip, hamming.hip, fuse.hip, sim3_match.hip and
+// sim3_solver.hip: the
+// omni projection (cayley2rot, M_t M_c, invMat, WorldToCamHom_fast / WorldToImg, ImgToWorld,
+// isPointInMirrorMask), the predicted pyramid level, the window
 // cell range of GetFeaturesInArea, the descriptor distance of a window candidate, the
 // wave-per-query window walk and CheckDistEpipolarLine.  One definition each, so every entry that
 // uses them gives the same bits.
@@ -113,6 +115,34 @@ __device__ inline void world_to_cam_img(const double* R, const double* t, const 
     Xc[i] = s;
   }
   world_to_img(cam, Xc[0], Xc[1], Xc[2], u, v);
+}
+
+// invMat (cConverter.cpp:31-44) of a row-major 4x4: R' = R^T, t' = -R' * t
+__device__ __forceinline__ void inv_mat44(const double* M, double* R, double* t) {
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) R[3 * i + j] = M[4 * j + i];
+  for (int i = 0; i < 3; i++) {
+    double s = 0.0;
+    for (int k = 0; k < 3; k++) s = __dadd_rn(s, __dmul_rn(-R[3 * i + k], M[4 * k + 3]));
+    t[i] = s;
+  }
+}
+
+// isPointInMirrorMask(u, v, 0) (cam_model_omni.cpp:165-180) on camera c's mask of
+// mask [n_cams][mh][mw]: cvRound, bounds (> 0 and < size), mask > 0
+__device__ __forceinline__ bool in_mirror_mask(const uint8_t* mask, int c, int mw, int mh, double u,
+                                               double v) {
+  const int ur = (int)rint(u), vr = (int)rint(v);
+  return !(ur >= mw || ur <= 0 || vr >= mh || vr <= 0) &&
+         mask[(int64_t)c * mw * mh + (int64_t)vr * mw + ur] != 0;
+}
+
+// nPredictedLevel = lower_bound(mvScaleFactors, dist / minDistance), capped at L - 1
+__device__ __forceinline__ int predict_level(const double* scale, int L, double ratio) {
+  int lv = 0;
+  while (lv < L && scale[lv] < ratio) lv++;
+  if (lv >= L) lv = L - 1;
+  return lv;
 }
 
 }  // namespace frm

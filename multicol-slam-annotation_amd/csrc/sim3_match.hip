@@ -14,6 +14,7 @@
 // so there is no host tail.  The window walk is win::walk_best of proj_window.hpp, shared with
 // k_fuse.  Compiled with -ffp-contract=off; every rounding follows the reference's expression
 // order (cv::Matx products: s = 0; s += a_k * b_k, k ascending).
+#include "host_util.hpp"
 #include "proj_window.hpp"
 #include <algorithm>
 #include <climits>
@@ -54,17 +55,6 @@ struct Args {
   int32_t* match1; int32_t* match2;
 };
 
-// invMat (cConverter.cpp:31-44) of a row-major 4x4: R' = R^T, t' = -R' * t
-__device__ inline void inv_mat(const double* M, double* R, double* t) {
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) R[3 * i + j] = M[4 * j + i];
-  for (int i = 0; i < 3; i++) {
-    double s = 0.0;
-    for (int k = 0; k < 3; k++) s = __dadd_rn(s, __dmul_rn(-R[3 * i + k], M[4 * k + 3]));
-    t[i] = s;
-  }
-}
-
 // Thread t < T: candidate t's T2 = GetPoseInverse (:1730), sR12, sR21, t21 (:1741-1743), and
 // n_found[t] = 0.  Thread T: KF1's T1 (:1729).  Threads T + 1 + c and T + 1 + C + c: invMat of
 // M_c[c] of KF1's rig and of the candidates' rig (:1889, :1795).
@@ -80,15 +70,15 @@ __global__ __launch_bounds__(64) void k_sim3_setup(const double* __restrict__ mt
                                                    int32_t* __restrict__ n_found) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx > T + 2 * C) return;
-  if (idx == T) { inv_mat(mt1, T1, T1 + 9); return; }
+  if (idx == T) { frm::inv_mat44(mt1, T1, T1 + 9); return; }
   if (idx > T) {
     const int c = idx - T - 1;
-    if (c < C) inv_mat(mc1 + 16 * c, imc1 + 12 * c, imc1 + 12 * c + 9);
-    else inv_mat(mc2 + 16 * (c - C), imc2 + 12 * (c - C), imc2 + 12 * (c - C) + 9);
+    if (c < C) frm::inv_mat44(mc1 + 16 * c, imc1 + 12 * c, imc1 + 12 * c + 9);
+    else frm::inv_mat44(mc2 + 16 * (c - C), imc2 + 12 * (c - C), imc2 + 12 * (c - C) + 9);
     return;
   }
   double* o = xf + kXf * (int64_t)idx;
-  inv_mat(mt2 + 16 * (int64_t)idx, o, o + 9);
+  frm::inv_mat44(mt2 + 16 * (int64_t)idx, o, o + 9);
   const double s = s12[idx], inv = __ddiv_rn(1.0, s);
   const double* R = R12 + 9 * (int64_t)idx;
   const double* tt = t12 + 3 * (int64_t)idx;
@@ -188,10 +178,7 @@ __global__ __launch_bounds__(256) void k_sim3_search(Args a) {
     bool go = !(pb[2] < 0.0);                 // the depth test is on the rig-frame z (:1798, :1892)
     if (go) {
       frm::world_to_img(a.k2.cam + 17 * c, pc[0], pc[1], pc[2], u, v);
-      // isPointInMirrorMask(u, v, 0): cvRound, bounds (> 0 and < size), mask > 0
-      const int ur = (int)rint(u), vr = (int)rint(v);
-      go = !(ur >= a.mw || ur <= 0 || vr >= a.mh || vr <= 0) &&
-           a.k2.mirror[(int64_t)c * a.mw * a.mh + (int64_t)vr * a.mw + ur] != 0;
+      go = frm::in_mirror_mask(a.k2.mirror, c, a.mw, a.mh, u, v);
     }
     if (go) {
       const double maxD = __dmul_rn(1.2, pt.dist[2 * gi + 1]);
@@ -200,10 +187,7 @@ __global__ __launch_bounds__(256) void k_sim3_search(Args a) {
                                             __dmul_rn(pc[2], pc[2])));
       go = !(d < minD || d > maxD);
       if (go) {
-        const double ratio = __ddiv_rn(d, minD);
-        lv = 0;
-        while (lv < a.L && to.scale[lv] < ratio) lv++;
-        if (lv >= a.L) lv = a.L - 1;
+        lv = frm::predict_level(to.scale, a.L, __ddiv_rn(d, minD));
         r = __dmul_rn(a.th, to.scale[lv]);
         go = win::cell_range(to.gp + 4 * c, u, v, r, &x0, &x1, &y0, &y1);
       }
@@ -241,25 +225,7 @@ __global__ __launch_bounds__(256) void k_sim3_agree(const int32_t* __restrict__ 
   if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(n_found + t, cnt);
 }
 
-// device allocations of one host-buffer call, released on every return path
-struct DevBufs {
-  std::vector<void*> p;
-  hipError_t err = hipSuccess;
-  template <class T> T* alloc(size_t n) {
-    void* q = nullptr;
-    if (err == hipSuccess) err = hipMalloc(&q, std::max<size_t>(1, n) * sizeof(T));
-    if (q) p.push_back(q);
-    return static_cast<T*>(q);
-  }
-  template <class T> T* up(const T* h, size_t n) {
-    T* d = alloc<T>(n);
-    if (err == hipSuccess && h && n) err = hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice);
-    return d;
-  }
-  ~DevBufs() { for (void* q : p) (void)hipFree(q); }
-};
-
-static int bad(const char* msg) { set_error(msg); return MCS_ERR_ARG; }
+using host::bad_arg;
 
 static bool set_has_nulls(const mcs_fuse_targets* k, bool grid) {
   if (!k->off || !k->m_t || !k->m_c || !k->cam || !k->mirror || !k->grid_params || !k->scale) return true;
@@ -272,46 +238,39 @@ static int check_args(const mcs_fuse_targets* k1, const mcs_sim3_points* p1, con
                       const mcs_sim3_points* p2, const void* act1, const void* act2, const void* s12,
                       const void* R12, const void* t12, const void* matches12, const void* n_found,
                       bool grid) {
-  if (!k1 || !p1 || !k2 || !p2) return bad("sim3: null keyframe set / points");
-  if (k1->bytes != 16 && k1->bytes != 32 && k1->bytes != 64) return bad("sim3: bytes must be 16, 32 or 64");
-  if (k1->n_cams < 1 || k1->n_cams > kMaxCams || k2->n_cams > kMaxCams) return bad("sim3: 1 to 8 cameras");
-  if (k1->n_targets != 1) return bad("sim3: kf1 must be a set of exactly one keyframe");
+  if (!k1 || !p1 || !k2 || !p2) return bad_arg("sim3: null keyframe set / points");
+  if (int rc = host::check_desc_bytes(k1->bytes, "sim3")) return rc;
+  if (k1->n_cams < 1 || k1->n_cams > kMaxCams || k2->n_cams > kMaxCams) return bad_arg("sim3: 1 to 8 cameras");
+  if (k1->n_targets != 1) return bad_arg("sim3: kf1 must be a set of exactly one keyframe");
   if (k1->n_cams != k2->n_cams || k1->bytes != k2->bytes || k1->n_levels != k2->n_levels ||
       k1->mirror_w != k2->mirror_w || k1->mirror_h != k2->mirror_h)
-    return bad("sim3: n_cams, bytes, n_levels and the mirror size of kf1 and kf2s must agree (shared rig)");
+    return bad_arg("sim3: n_cams, bytes, n_levels and the mirror size of kf1 and kf2s must agree (shared rig)");
   if (k2->n_targets < 0 || k1->n_kp_total < 0 || k2->n_kp_total < 0 || k1->n_levels < 1 ||
       k1->mirror_w < 1 || k1->mirror_h < 1)
-    return bad("sim3: negative count or empty pyramid / mirror mask");
+    return bad_arg("sim3: negative count or empty pyramid / mirror mask");
   if (p1->n != k1->n_kp_total || p2->n != k2->n_kp_total)
-    return bad("sim3: the points must hold one slot per keypoint of their set");
+    return bad_arg("sim3: the points must hold one slot per keypoint of their set");
   // an empty side has no rows to point at: the sides that hold keypoints must agree
   int with = 0, sides = 0;
   if (k1->n_kp_total > 0) { sides += 2; with += (k1->mask != nullptr) + (p1->mask != nullptr); }
   if (k2->n_kp_total > 0) { sides += 2; with += (k2->mask != nullptr) + (p2->mask != nullptr); }
   if (with != 0 && with != sides)
-    return bad("sim3: descriptor masks for both keyframe sets and both point sets, or for none");
-  if (k1->n_kp_total >= kMaxKp) return bad("sim3: keypoints per keyframe must be below 2^19 (position field of the key)");
+    return bad_arg("sim3: descriptor masks for both keyframe sets and both point sets, or for none");
+  if (k1->n_kp_total >= kMaxKp) return bad_arg("sim3: keypoints per keyframe must be below 2^19 (position field of the key)");
   if ((int64_t)k2->n_targets * k1->n_kp_total + k2->n_kp_total >= (int64_t)INT_MAX)
-    return bad("sim3: batch too large for one launch");
+    return bad_arg("sim3: batch too large for one launch");
   if (k2->n_targets == 0) return MCS_OK;
   if (set_has_nulls(k1, grid) || set_has_nulls(k2, grid) || !s12 || !R12 || !t12 || !n_found ||
       (k1->n_kp_total > 0 && (!p1->pos || !p1->dist || !p1->desc || !act1 || !matches12)) ||
       (k2->n_kp_total > 0 && (!p2->pos || !p2->dist || !p2->desc || !act2)))
-    return bad("sim3: null buffer");
+    return bad_arg("sim3: null buffer");
   return MCS_OK;
 }
 
 // the host entry sees the offsets and the cameras
 static int check_host_set(const mcs_fuse_targets* k) {
-  const int T = k->n_targets;
-  if (k->off[0] != 0 || k->off[T] != k->n_kp_total) return bad("sim3: off[0] must be 0 and off[n_targets] n_kp_total");
-  for (int t = 0; t < T; t++) {
-    if (k->off[t + 1] < k->off[t]) return bad("sim3: offsets must be non-decreasing");
-    if (k->off[t + 1] - k->off[t] >= kMaxKp) return bad("sim3: keypoints per keyframe must be below 2^19 (position field of the key)");
-  }
-  for (int i = 0; i < k->n_kp_total; i++)
-    if (k->kp_cam[i] < 0 || k->kp_cam[i] >= k->n_cams) return bad("sim3: kp_cam outside [0, n_cams)");
-  return MCS_OK;
+  if (int rc = host::check_set_offsets(k->off, k->n_targets, k->n_kp_total, kMaxKp, "sim3")) return rc;
+  return host::check_kp_cam(k->kp_cam, k->n_kp_total, k->n_cams, "sim3");
 }
 
 static Set dev_set(const mcs_fuse_targets* k) {
@@ -339,13 +298,7 @@ int mcs_sim3_workspace_create(int32_t device, int32_t max_targets, int32_t max_k
     set_error("sim3 workspace: bad argument");
     return MCS_ERR_ARG;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("no HIP device visible (no CPU fallback)");
-    return MCS_ERR_NO_DEVICE;
-  }
-  if (device < 0 || device >= ndev) { set_error("sim3 workspace: no such device"); return MCS_ERR_ARG; }
-  MCS_HIP_CHECK(hipSetDevice(device));
+  if (int rc = host::open_device(device, "sim3 workspace")) return rc;
   mcs_sim3_workspace* w = new mcs_sim3_workspace;
   w->device = device;
   w->max_targets = max_targets;
@@ -391,7 +344,7 @@ int mcs_search_by_sim3_device(mcs_sim3_workspace* ws, const mcs_fuse_targets* kf
     int dev = 0;
     MCS_HIP_CHECK(hipGetDevice(&dev));
     const int64_t per = std::max<int64_t>(std::max<int64_t>(n1, (n2 + T - 1) / T), 1);
-    if (per >= sim3::kMaxKp) return sim3::bad("sim3: keypoints per keyframe must be below 2^19 (position field of the key)");
+    if (per >= sim3::kMaxKp) return host::bad_arg("sim3: keypoints per keyframe must be below 2^19 (position field of the key)");
     rc = mcs_sim3_workspace_create(dev, T, (int32_t)per, &tmp);
     if (rc) return rc;
     ws = tmp;
@@ -437,58 +390,25 @@ int mcs_search_by_sim3(int32_t device, const mcs_fuse_targets* kf1, const mcs_si
   int rc = sim3::check_args(kf1, pts1, kf2s, pts2, active1, active2, s12, R12, t12, matches12, n_found,
                             false);
   if (rc) return rc;
-  const int T = kf2s->n_targets, C = kf1->n_cams;
+  const int T = kf2s->n_targets;
   if (T == 0) return MCS_OK;
   if ((rc = sim3::check_host_set(kf1)) || (rc = sim3::check_host_set(kf2s))) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("no HIP device visible (no CPU fallback)");
-    return MCS_ERR_NO_DEVICE;
-  }
-  if (device < 0 || device >= ndev) return sim3::bad("sim3: no such device");
-  MCS_HIP_CHECK(hipSetDevice(device));
-  const size_t ncell = (size_t)C * sim3::kCells, nb = (size_t)kf1->bytes;
+  if ((rc = host::open_device(device, "sim3"))) return rc;
+  const size_t nb = (size_t)kf1->bytes;
   const size_t n1 = (size_t)kf1->n_kp_total, n2 = (size_t)kf2s->n_kp_total;
-  sim3::DevBufs B;
-  std::vector<int32_t> cell_ptr, cell_kp;
-  auto upload = [&](const mcs_fuse_targets* k, const mcs_sim3_points* p, mcs_sim3_points* dp) -> mcs_fuse_targets {
-    const int Tk = k->n_targets;
+  host::DevBufs B;
+  auto upload = [&](const mcs_fuse_targets* k, const mcs_sim3_points* p, mcs_fuse_targets* d, mcs_sim3_points* dp) {
     const size_t nk = (size_t)k->n_kp_total;
-    cell_ptr.assign((size_t)Tk * (ncell + 1), 0);
-    cell_kp.assign(std::max<size_t>(1, nk), 0);
-    for (int t = 0; t < Tk && rc == MCS_OK; t++) {
-      const size_t o = (size_t)k->off[t];
-      rc = mcs_frame_grid_build(k->kp_xy ? k->kp_xy + 2 * o : nullptr, k->kp_cam ? k->kp_cam + o : nullptr,
-                                k->off[t + 1] - k->off[t], C, k->grid_params,
-                                cell_ptr.data() + (size_t)t * (ncell + 1), cell_kp.data() + o, nullptr);
-    }
-    mcs_fuse_targets d = *k;
-    d.off = B.up(k->off, (size_t)Tk + 1);
-    d.kp_xy = B.up(k->kp_xy, 2 * nk);
-    d.kp_octave = B.up(k->kp_octave, nk);
-    d.kp_cam = B.up(k->kp_cam, nk);
-    d.desc = B.up(k->desc, nk * nb);
-    d.mask = k->mask ? B.up(k->mask, nk * nb) : nullptr;
-    d.rays = nullptr;
-    d.m_t = B.up(k->m_t, 16 * (size_t)Tk);
-    d.m_c = B.up(k->m_c, 16 * (size_t)C);
-    d.cam = B.up(k->cam, 17 * (size_t)C);
-    d.mirror = B.up(k->mirror, (size_t)C * k->mirror_w * k->mirror_h);
-    d.grid_params = B.up(k->grid_params, 4 * (size_t)C);
-    d.scale = B.up(k->scale, (size_t)k->n_levels);
-    d.cell_ptr = B.up(cell_ptr.data(), cell_ptr.size());
-    d.cell_kp = B.up(cell_kp.data(), cell_kp.size());
     *dp = *p;
     dp->pos = B.up(p->pos, 3 * nk);
     dp->dist = B.up(p->dist, 2 * nk);
     dp->desc = B.up(p->desc, nk * nb);
-    dp->mask = p->mask ? B.up(p->mask, nk * nb) : nullptr;
-    return d;
+    dp->mask = B.up(p->mask, nk * nb);
+    return host::upload_kf_set(B, *k, host::kKfSearch | host::kKfCam, d);
   };
+  mcs_fuse_targets d1, d2;
   mcs_sim3_points dp1, dp2;
-  const mcs_fuse_targets d1 = upload(kf1, pts1, &dp1);
-  const mcs_fuse_targets d2 = upload(kf2s, pts2, &dp2);
-  if (rc) { set_error("sim3: grid build failed"); return rc; }
+  if ((rc = upload(kf1, pts1, &d1, &dp1)) || (rc = upload(kf2s, pts2, &d2, &dp2))) return rc;
   const uint8_t* d_a1 = B.up(active1, (size_t)T * n1);
   const uint8_t* d_a2 = B.up(active2, n2);
   const double* d_s = B.up(s12, (size_t)T);
@@ -502,10 +422,11 @@ int mcs_search_by_sim3(int32_t device, const mcs_fuse_targets* kf1, const mcs_si
   rc = mcs_search_by_sim3_device(nullptr, &d1, &dp1, &d2, &dp2, d_a1, d_a2, d_s, d_R, d_t, th, th_high,
                                  d_m1, d_m2, d_m12, d_nf, nullptr);
   if (rc) return rc;
-  if (match1 && n1) MCS_HIP_CHECK(hipMemcpy(match1, d_m1, 4 * (size_t)T * n1, hipMemcpyDeviceToHost));
-  if (match2 && n2) MCS_HIP_CHECK(hipMemcpy(match2, d_m2, 4 * n2, hipMemcpyDeviceToHost));
-  if (n1) MCS_HIP_CHECK(hipMemcpy(matches12, d_m12, 4 * (size_t)T * n1, hipMemcpyDeviceToHost));
-  MCS_HIP_CHECK(hipMemcpy(n_found, d_nf, 4 * (size_t)T, hipMemcpyDeviceToHost));
+  B.down(match1, d_m1, (size_t)T * n1);
+  B.down(match2, d_m2, n2);
+  B.down(matches12, d_m12, (size_t)T * n1);
+  B.down(n_found, d_nf, (size_t)T);
+  if (B.err != hipSuccess) { set_hip_error(B.err, "sim3 download", __FILE__, __LINE__); return MCS_ERR_HIP; }
   return MCS_OK;
 }
 

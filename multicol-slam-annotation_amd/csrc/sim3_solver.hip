@@ -19,6 +19,7 @@
 // Compiled with -ffp-contract=off; the prepare and check kernels follow the reference's
 // expression order (cv::Matx products: s = 0; s += a_k * b_k, k ascending).  cv::eigen and
 // cv::Rodrigues are OpenCV internals: the hypothesis is Horn's solution to rounding, not bitwise.
+#include "host_util.hpp"
 #include "proj_window.hpp"
 #include "sim3_draws.hpp"
 #include <algorithm>
@@ -60,17 +61,6 @@ struct Ransac {
 };
 
 struct Work { double* hyp; uint64_t* words; int32_t* inl; double* imc; };
-
-// invMat (cConverter.cpp:31-44) of a row-major 4x4: R' = R^T, t' = -R' * t
-__device__ inline void inv_mat(const double* M, double* R, double* t) {
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) R[3 * i + j] = M[4 * j + i];
-  for (int i = 0; i < 3; i++) {
-    double s = 0.0;
-    for (int k = 0; k < 3; k++) s = __dadd_rn(s, __dmul_rn(-R[3 * i + k], M[4 * k + 3]));
-    t[i] = s;
-  }
-}
 
 // y = A * x + b: the Matx33d * Vec3d product (s = 0; s += a(i,k) x(k)), then the Vec sum
 __device__ __forceinline__ void rot_add(const double* A, const double* x, const double* b, double* y) {
@@ -119,8 +109,8 @@ __global__ __launch_bounds__(kPrep) void k_s3s_prepare(Set k1, Set k2, const dou
   const int n_1 = min(min(max(k1.off[1] - o1, 0), k1.n_kp_total - o1), n1);
   const int o2 = min(max(k2.off[t], 0), k2.n_kp_total);
   const int n_2 = min(max(k2.off[t + 1] - o2, 0), k2.n_kp_total - o2);
-  if (threadIdx.x == 0) inv_mat(k1.m_t, s_h, s_h + 9);
-  if (threadIdx.x == 64) inv_mat(k2.m_t + 16 * (int64_t)t, s_h + 12, s_h + 21);
+  if (threadIdx.x == 0) frm::inv_mat44(k1.m_t, s_h, s_h + 9);
+  if (threadIdx.x == 64) frm::inv_mat44(k2.m_t + 16 * (int64_t)t, s_h + 12, s_h + 21);
   __syncthreads();
   int base = 0;
   for (int i0 = 0; i0 < n1; i0 += kPrep) {
@@ -189,7 +179,7 @@ __global__ __launch_bounds__(256) void k_s3s_params(int T, int C, int n1, int W,
   if (idx >= T + C) return;
   if (idx >= T) {
     const int c = (int)idx - T;
-    inv_mat(m_c + 16 * c, imc + 12 * c, imc + 12 * c + 9);
+    frm::inv_mat44(m_c + 16 * c, imc + 12 * c, imc + 12 * c + 9);
     return;
   }
   if (!flags) return;
@@ -529,34 +519,16 @@ __global__ __launch_bounds__(256) void k_s3s_active_clear(int n1, int n2, const 
   if (f >= 0 && f < n_2) active2[o2 + f] = 0;
 }
 
-// device allocations of one host-buffer call, released on every return path
-struct DevBufs {
-  std::vector<void*> p;
-  hipError_t err = hipSuccess;
-  template <class T> T* alloc(size_t n) {
-    void* q = nullptr;
-    if (err == hipSuccess) err = hipMalloc(&q, std::max<size_t>(1, n) * sizeof(T));
-    if (q) p.push_back(q);
-    return static_cast<T*>(q);
-  }
-  template <class T> T* up(const T* h, size_t n) {
-    T* d = alloc<T>(n);
-    if (err == hipSuccess && h && n) err = hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice);
-    return d;
-  }
-  ~DevBufs() { for (void* q : p) (void)hipFree(q); }
-};
-
-static int bad(const char* msg) { set_error(msg); return MCS_ERR_ARG; }
+using host::bad_arg;
 
 static int check_sets(const mcs_fuse_targets* k1, const mcs_fuse_targets* k2) {
-  if (!k1 || !k2) return bad("sim3 solver: null keyframe set");
-  if (k1->n_targets != 1) return bad("sim3 solver: kf1 must be a set of exactly one keyframe");
+  if (!k1 || !k2) return bad_arg("sim3 solver: null keyframe set");
+  if (k1->n_targets != 1) return bad_arg("sim3 solver: kf1 must be a set of exactly one keyframe");
   if (k1->n_cams < 1 || k1->n_cams > kMaxCams || k1->n_cams != k2->n_cams || k1->n_levels != k2->n_levels)
-    return bad("sim3 solver: 1 to 8 cameras; n_cams and n_levels of kf1 and kf2s must agree (shared rig)");
+    return bad_arg("sim3 solver: 1 to 8 cameras; n_cams and n_levels of kf1 and kf2s must agree (shared rig)");
   if (k2->n_targets < 0 || k1->n_kp_total < 0 || k2->n_kp_total < 0 || k1->n_levels < 1)
-    return bad("sim3 solver: negative count or empty pyramid");
-  if (k1->n_kp_total >= kMaxKp) return bad("sim3 solver: keypoints per keyframe must be below 2^19");
+    return bad_arg("sim3 solver: negative count or empty pyramid");
+  if (k1->n_kp_total >= kMaxKp) return bad_arg("sim3 solver: keypoints per keyframe must be below 2^19");
   return MCS_OK;
 }
 
@@ -569,41 +541,41 @@ static int check_prepare(const mcs_fuse_targets* k1, const mcs_sim3_points* p1, 
                          const void* f1, const void* f2, const void* sigma2, const mcs_sim3_corr* c) {
   int rc = check_sets(k1, k2);
   if (rc) return rc;
-  if (!p1 || !p2 || !c) return bad("sim3 solver: null points / correspondences");
+  if (!p1 || !p2 || !c) return bad_arg("sim3 solver: null points / correspondences");
   if (p1->n != k1->n_kp_total || p2->n != k2->n_kp_total)
-    return bad("sim3 solver: the points must hold one slot per keypoint of their set");
+    return bad_arg("sim3 solver: the points must hold one slot per keypoint of their set");
   if (c->n_targets != k2->n_targets || c->cap != k1->n_kp_total || c->n_cams != k1->n_cams)
-    return bad("sim3 solver: correspondences need n_targets = T, cap = n1 and n_cams of the rig");
+    return bad_arg("sim3 solver: correspondences need n_targets = T, cap = n1 and n_cams of the rig");
   if (k2->n_targets == 0) return MCS_OK;
-  if (set_nulls(k1) || set_nulls(k2) || !sigma2 || !c->n) return bad("sim3 solver: null buffer");
+  if (set_nulls(k1) || set_nulls(k2) || !sigma2 || !c->n) return bad_arg("sim3 solver: null buffer");
   if (k1->n_kp_total > 0 &&
       (!p1->pos || !m12 || !ok1 || !f1 || !c->idx1 || !c->X1 || !c->X2 || !c->p1 || !c->p2 || !c->cam1 ||
        !c->cam2 || !c->maxerr1 || !c->maxerr2))
-    return bad("sim3 solver: null buffer");
-  if (k2->n_kp_total > 0 && (!p2->pos || !ok2 || !f2)) return bad("sim3 solver: null buffer");
+    return bad_arg("sim3 solver: null buffer");
+  if (k2->n_kp_total > 0 && (!p2->pos || !ok2 || !f2)) return bad_arg("sim3 solver: null buffer");
   return MCS_OK;
 }
 
 static int check_iterate(const mcs_sim3_corr* c, const void* samples, int n_it, double prob, int min_inl,
                          int cap_its, int flags, const mcs_sim3_ransac* r, bool host) {
-  if (!c || !r) return bad("sim3 solver: null correspondences / state");
+  if (!c || !r) return bad_arg("sim3 solver: null correspondences / state");
   if (c->n_targets < 0 || c->cap < 0 || c->cap >= kMaxKp || c->n_cams < 1 || c->n_cams > kMaxCams)
-    return bad("sim3 solver: bad correspondence set");
-  if (n_it < 1 || cap_its < 1 || n_it > cap_its) return bad("sim3 solver: 1 <= n_iterations <= max_its_cap");
-  if (min_inl < 1) return bad("sim3 solver: min_inliers must be at least 1");
-  if (!(prob > 0.0 && prob < 1.0)) return bad("sim3 solver: probability must lie inside (0, 1)");
-  if (flags & ~(MCS_SIM3_INIT | MCS_SIM3_SET_PARAMS)) return bad("sim3 solver: unknown flag");
+    return bad_arg("sim3 solver: bad correspondence set");
+  if (n_it < 1 || cap_its < 1 || n_it > cap_its) return bad_arg("sim3 solver: 1 <= n_iterations <= max_its_cap");
+  if (min_inl < 1) return bad_arg("sim3 solver: min_inliers must be at least 1");
+  if (!(prob > 0.0 && prob < 1.0)) return bad_arg("sim3 solver: probability must lie inside (0, 1)");
+  if (flags & ~(MCS_SIM3_INIT | MCS_SIM3_SET_PARAMS)) return bad_arg("sim3 solver: unknown flag");
   if ((int64_t)c->n_targets * cap_its >= INT_MAX / 4 || (int64_t)c->n_targets * std::max(c->cap, 1) >= INT_MAX / 2)
-    return bad("sim3 solver: batch too large for one launch");
+    return bad_arg("sim3 solver: batch too large for one launch");
   if (c->n_targets == 0) return MCS_OK;
   if (!samples || !r->iterations || !r->best_inliers || !r->max_its || !r->s12 || !r->R12 || !r->t12 ||
       !r->T12 || !r->success || !r->no_more || !r->n_inliers)
-    return bad("sim3 solver: null buffer");
-  if (!host && (!c->m_c || !c->cam || !c->n)) return bad("sim3 solver: null buffer");
-  if (c->cap > 0 && (!r->best_words || !r->inlier)) return bad("sim3 solver: null buffer");
+    return bad_arg("sim3 solver: null buffer");
+  if (!host && (!c->m_c || !c->cam || !c->n)) return bad_arg("sim3 solver: null buffer");
+  if (c->cap > 0 && (!r->best_words || !r->inlier)) return bad_arg("sim3 solver: null buffer");
   if (!host && c->cap > 0 &&
       (!c->idx1 || !c->X1 || !c->X2 || !c->p1 || !c->p2 || !c->cam1 || !c->cam2 || !c->maxerr1 || !c->maxerr2))
-    return bad("sim3 solver: null buffer");
+    return bad_arg("sim3 solver: null buffer");
   return MCS_OK;
 }
 
@@ -637,8 +609,8 @@ struct mcs_sim3_solver_workspace {
 extern "C" {
 
 int mcs_sim3_draw_samples(int32_t n, const int32_t* draws, int32_t n_its, int32_t* samples) {
-  if (n_its < 0 || (n_its > 0 && (!draws || !samples))) return s3s::bad("sim3 draws: null buffer or negative count");
-  if (sim3_draw_samples(n, draws, n_its, samples)) return s3s::bad("sim3 draws: n >= 3 and every draw inside [0, n)");
+  if (n_its < 0 || (n_its > 0 && (!draws || !samples))) return host::bad_arg("sim3 draws: null buffer or negative count");
+  if (sim3_draw_samples(n, draws, n_its, samples)) return host::bad_arg("sim3 draws: n >= 3 and every draw inside [0, n)");
   return MCS_OK;
 }
 
@@ -649,13 +621,7 @@ int mcs_sim3_solver_workspace_create(int32_t device, int32_t max_targets, int32_
     set_error("sim3 solver workspace: bad argument");
     return MCS_ERR_ARG;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("no HIP device visible (no CPU fallback)");
-    return MCS_ERR_NO_DEVICE;
-  }
-  if (device < 0 || device >= ndev) { set_error("sim3 solver workspace: no such device"); return MCS_ERR_ARG; }
-  MCS_HIP_CHECK(hipSetDevice(device));
+  if (int rc = host::open_device(device, "sim3 solver workspace")) return rc;
   mcs_sim3_solver_workspace* w = new mcs_sim3_solver_workspace;
   w->device = device;
   w->max_targets = max_targets;
@@ -749,15 +715,15 @@ int mcs_sim3_solver_active_device(const mcs_fuse_targets* kf1, const mcs_fuse_ta
                                   const uint8_t* d_inlier, const uint8_t* d_good1, const uint8_t* d_good2,
                                   const int32_t* d_matches12, const int32_t* d_first2, uint8_t* d_active1,
                                   uint8_t* d_active2, void* stream) {
-  if (!kf1 || !kf2s) return s3s::bad("sim3 solver: null keyframe set");
+  if (!kf1 || !kf2s) return host::bad_arg("sim3 solver: null keyframe set");
   if (kf1->n_targets != 1 || kf2s->n_targets < 0 || kf1->n_kp_total < 0 || kf2s->n_kp_total < 0)
-    return s3s::bad("sim3 solver: kf1 must be a set of exactly one keyframe; no negative counts");
+    return host::bad_arg("sim3 solver: kf1 must be a set of exactly one keyframe; no negative counts");
   const int T = kf2s->n_targets, n1 = kf1->n_kp_total, n2 = kf2s->n_kp_total;
-  if ((int64_t)T * n1 + n2 >= (int64_t)INT_MAX) return s3s::bad("sim3 solver: batch too large for one launch");
+  if ((int64_t)T * n1 + n2 >= (int64_t)INT_MAX) return host::bad_arg("sim3 solver: batch too large for one launch");
   if (T == 0) return MCS_OK;
   if (!kf2s->off || (n1 > 0 && (!d_inlier || !d_good1 || !d_matches12 || !d_active1)) ||
       (n2 > 0 && (!d_good2 || !d_active2 || (n1 > 0 && !d_first2))))
-    return s3s::bad("sim3 solver: null buffer");
+    return host::bad_arg("sim3 solver: null buffer");
   hipStream_t st = (hipStream_t)stream;
   const int64_t nt = (int64_t)T * n1 + n2;
   if (nt > 0)
@@ -789,43 +755,24 @@ int mcs_sim3_solver(int32_t device, const mcs_fuse_targets* kf1, const mcs_sim3_
   if ((rc = s3s::check_prepare(kf1, pts1, kf2s, pts2, matches12, ok1, ok2, first1, first2, sigma2, &full))) return rc;
   if ((rc = s3s::check_iterate(&full, samples, n_iterations, prob, min_inliers, max_its_cap, flags, ransac, true)))
     return rc;
-  const int T = kf2s->n_targets, C = kf1->n_cams;
+  const int T = kf2s->n_targets;
   const size_t n1 = (size_t)kf1->n_kp_total, n2 = (size_t)kf2s->n_kp_total;
   if ((active1 || active2) && ((n1 > 0 && (!good1 || !active1)) || (n2 > 0 && (!good2 || !active2))))
-    return s3s::bad("sim3 solver: the hand-over needs good1, good2, active1 and active2");
+    return host::bad_arg("sim3 solver: the hand-over needs good1, good2, active1 and active2");
   if (T == 0) return MCS_OK;
-  for (const mcs_fuse_targets* k : {kf1, kf2s}) {
-    if (k->off[0] != 0 || k->off[k->n_targets] != k->n_kp_total)
-      return s3s::bad("sim3 solver: off[0] must be 0 and off[n_targets] n_kp_total");
-    for (int t = 0; t < k->n_targets; t++)
-      if (k->off[t + 1] < k->off[t]) return s3s::bad("sim3 solver: offsets must be non-decreasing");
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("no HIP device visible (no CPU fallback)");
-    return MCS_ERR_NO_DEVICE;
-  }
-  if (device < 0 || device >= ndev) return s3s::bad("sim3 solver: no such device");
-  MCS_HIP_CHECK(hipSetDevice(device));
-  s3s::DevBufs B;
-  auto upload = [&](const mcs_fuse_targets* k, const mcs_sim3_points* p, mcs_sim3_points* dp) {
-    const size_t nk = (size_t)k->n_kp_total;
-    mcs_fuse_targets d = *k;
-    d.off = B.up(k->off, (size_t)k->n_targets + 1);
-    d.kp_octave = B.up(k->kp_octave, nk);
-    d.kp_cam = B.up(k->kp_cam, nk);
-    d.m_t = B.up(k->m_t, 16 * (size_t)k->n_targets);
-    d.m_c = B.up(k->m_c, 16 * (size_t)C);
-    d.cam = B.up(k->cam, 17 * (size_t)C);
-    d.kp_xy = nullptr; d.desc = d.mask = d.mirror = nullptr; d.rays = d.grid_params = d.scale = nullptr;
-    d.cell_ptr = d.cell_kp = nullptr;
+  for (const mcs_fuse_targets* k : {kf1, kf2s})
+    if ((rc = host::check_set_offsets(k->off, k->n_targets, k->n_kp_total, 0, "sim3 solver"))) return rc;
+  if ((rc = host::open_device(device, "sim3 solver"))) return rc;
+  host::DevBufs B;
+  auto upload = [&](const mcs_fuse_targets* k, const mcs_sim3_points* p, mcs_fuse_targets* d, mcs_sim3_points* dp) {
     *dp = *p;
-    dp->pos = B.up(p->pos, 3 * nk);
+    dp->pos = B.up(p->pos, 3 * (size_t)k->n_kp_total);
     dp->dist = nullptr; dp->desc = dp->mask = nullptr;
-    return d;
+    return host::upload_kf_set(B, *k, host::kKfCam, d);   // no search: neither grids nor descriptors
   };
+  mcs_fuse_targets d1, d2;
   mcs_sim3_points dp1, dp2;
-  const mcs_fuse_targets d1 = upload(kf1, pts1, &dp1), d2 = upload(kf2s, pts2, &dp2);
+  if ((rc = upload(kf1, pts1, &d1, &dp1)) || (rc = upload(kf2s, pts2, &d2, &dp2))) return rc;
   const size_t nr = (size_t)T * n1, W = (n1 + 63) / 64, nh = (size_t)T * n_iterations;
   const int32_t* d_m12 = B.up(matches12, nr);
   const uint8_t* d_ok1 = B.up(ok1, n1);
@@ -865,35 +812,33 @@ int mcs_sim3_solver(int32_t device, const mcs_fuse_targets* kf1, const mcs_sim3_
   if (hand && (rc = mcs_sim3_solver_active_device(&d1, &d2, dr.inlier, d_g1, d_g2, d_m12, d_f2, d_a1, d_a2, nullptr)))
     return rc;
   MCS_HIP_CHECK(hipDeviceSynchronize());
-  auto down = [&](auto* h, const auto* d, size_t n) -> hipError_t {
-    return (h && n) ? hipMemcpy(h, d, n * sizeof(*h), hipMemcpyDeviceToHost) : hipSuccess;
-  };
-  MCS_HIP_CHECK(down(hc.n, dc.n, (size_t)T));
-  MCS_HIP_CHECK(down(hc.idx1, dc.idx1, nr));
-  MCS_HIP_CHECK(down(hc.cam1, dc.cam1, nr));
-  MCS_HIP_CHECK(down(hc.cam2, dc.cam2, nr));
-  MCS_HIP_CHECK(down(hc.X1, dc.X1, 3 * nr));
-  MCS_HIP_CHECK(down(hc.X2, dc.X2, 3 * nr));
-  MCS_HIP_CHECK(down(hc.p1, dc.p1, 2 * nr));
-  MCS_HIP_CHECK(down(hc.p2, dc.p2, 2 * nr));
-  MCS_HIP_CHECK(down(hc.maxerr1, dc.maxerr1, nr));
-  MCS_HIP_CHECK(down(hc.maxerr2, dc.maxerr2, nr));
-  MCS_HIP_CHECK(down(ransac->iterations, dr.iterations, (size_t)T));
-  MCS_HIP_CHECK(down(ransac->best_inliers, dr.best_inliers, (size_t)T));
-  MCS_HIP_CHECK(down(ransac->max_its, dr.max_its, (size_t)T));
-  MCS_HIP_CHECK(down(ransac->best_words, dr.best_words, T * W));
-  MCS_HIP_CHECK(down(ransac->s12, dr.s12, (size_t)T));
-  MCS_HIP_CHECK(down(ransac->R12, dr.R12, 9 * (size_t)T));
-  MCS_HIP_CHECK(down(ransac->t12, dr.t12, 3 * (size_t)T));
-  MCS_HIP_CHECK(down(ransac->T12, dr.T12, 16 * (size_t)T));
-  MCS_HIP_CHECK(down(ransac->success, dr.success, (size_t)T));
-  MCS_HIP_CHECK(down(ransac->no_more, dr.no_more, (size_t)T));
-  MCS_HIP_CHECK(down(ransac->n_inliers, dr.n_inliers, (size_t)T));
-  MCS_HIP_CHECK(down(ransac->inlier, dr.inlier, nr));
-  MCS_HIP_CHECK(down(ransac->hyp_srt, dr.hyp_srt, 13 * nh));
-  MCS_HIP_CHECK(down(ransac->hyp_inl, dr.hyp_inl, nh));
-  MCS_HIP_CHECK(down(active1, d_a1, nr));
-  MCS_HIP_CHECK(down(active2, d_a2, n2));
+  B.down(hc.n, dc.n, (size_t)T);
+  B.down(hc.idx1, dc.idx1, nr);
+  B.down(hc.cam1, dc.cam1, nr);
+  B.down(hc.cam2, dc.cam2, nr);
+  B.down(hc.X1, dc.X1, 3 * nr);
+  B.down(hc.X2, dc.X2, 3 * nr);
+  B.down(hc.p1, dc.p1, 2 * nr);
+  B.down(hc.p2, dc.p2, 2 * nr);
+  B.down(hc.maxerr1, dc.maxerr1, nr);
+  B.down(hc.maxerr2, dc.maxerr2, nr);
+  B.down(ransac->iterations, dr.iterations, (size_t)T);
+  B.down(ransac->best_inliers, dr.best_inliers, (size_t)T);
+  B.down(ransac->max_its, dr.max_its, (size_t)T);
+  B.down(ransac->best_words, dr.best_words, T * W);
+  B.down(ransac->s12, dr.s12, (size_t)T);
+  B.down(ransac->R12, dr.R12, 9 * (size_t)T);
+  B.down(ransac->t12, dr.t12, 3 * (size_t)T);
+  B.down(ransac->T12, dr.T12, 16 * (size_t)T);
+  B.down(ransac->success, dr.success, (size_t)T);
+  B.down(ransac->no_more, dr.no_more, (size_t)T);
+  B.down(ransac->n_inliers, dr.n_inliers, (size_t)T);
+  B.down(ransac->inlier, dr.inlier, nr);
+  B.down(ransac->hyp_srt, dr.hyp_srt, 13 * nh);
+  B.down(ransac->hyp_inl, dr.hyp_inl, nh);
+  B.down(active1, d_a1, nr);
+  B.down(active2, d_a2, n2);
+  if (B.err != hipSuccess) { set_hip_error(B.err, "sim3 solver download", __FILE__, __LINE__); return MCS_ERR_HIP; }
   return MCS_OK;
 }
 

@@ -21,7 +21,7 @@
 // the winner; the ancestor at level L - levelsup is recorded on the way down.  The descent is
 // integer VALU work (v_xor + v_bcnt per dword) on L2-resident gathers; roofline: the
 // descriptor stream (32 B in, 16 B out per feature) from HBM.
-#include "common.hpp"
+#include "host_util.hpp"
 #include "../../include/mcs_vocab.h"
 #include <algorithm>
 #include <cmath>
@@ -156,13 +156,7 @@ int mcs_vocab_create(int32_t k, int32_t L, int32_t scoring, int32_t weighting, i
     }
     if (v > 0) wt[v] = weight[pos[v]];
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("no HIP device visible (no CPU fallback)");
-    return MCS_ERR_NO_DEVICE;
-  }
-  if (device < 0 || device >= ndev) return MCS_ERR_ARG;
-  MCS_HIP_CHECK(hipSetDevice(device));
+  if (int rc = host::open_device(device, "vocab")) return rc;
   mcs_vocab* V = new mcs_vocab();
   V->k = k; V->L = L; V->scoring = scoring; V->weighting = weighting;
   V->n_nodes = nn; V->n_words = n_words; V->device = device;

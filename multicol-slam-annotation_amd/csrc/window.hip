@@ -1,6 +1,7 @@
 // Projection-guided (windowed) matching: the cMultiFrame feature grid on the host, then
 // GetFeaturesInArea and the Hamming distance of every window candidate on the device, then the
-// reference's sequential best / second-best selection rules on the host.
+// reference's sequential best / second-best selection rules on the host.  The two host steps
+// (mcs_frame_grid_build, mcs_window_select) are window_host.cpp.
 //
 // Reference (billamiable/MultiCol-SLAM-Annotation):
 //   grid build (part of the cMultiFrame ctor)            src/cMultiFrame.cpp:154-184
@@ -14,6 +15,7 @@
 // checkOrientation is false in the reference (include/cORBmatcher.h:40), so no rotation
 // histograms.  GetFeaturesInArea's abs(kp.pt.x - x) is the double overload (the operand is a
 // double), i.e. fabs.
+#include "host_util.hpp"
 #include "proj_window.hpp"
 #include "../../include/mcs_matcher.h"
 #include <algorithm>
@@ -122,56 +124,12 @@ __global__ __launch_bounds__(1024) void k_scan(int32_t* p, int nq, int64_t* tota
   if (threadIdx.x == 0) *total = carry;
 }
 
-// device allocations of one host-buffer call, released on every return path
-struct DevBufs {
-  std::vector<void*> p;
-  hipError_t err = hipSuccess;
-  template <class T> T* alloc(size_t n) {
-    void* q = nullptr;
-    if (err == hipSuccess) err = hipMalloc(&q, std::max<size_t>(1, n) * sizeof(T));
-    if (q) p.push_back(q);
-    return static_cast<T*>(q);
-  }
-  template <class T> T* up(const T* h, size_t n) {
-    T* d = alloc<T>(n);
-    if (err == hipSuccess && h && n) err = hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice);
-    return d;
-  }
-  ~DevBufs() { for (void* q : p) (void)hipFree(q); }
-};
-
 }  // namespace win
 }  // namespace mcs
 
 using namespace mcs;
 
 extern "C" {
-
-int mcs_frame_grid_build(const float* kp_xy, const int32_t* kp_cam, int32_t n_kp, int32_t n_cams,
-                         const double* gp, int32_t* cell_ptr, int32_t* cell_kp,
-                         int32_t* n_in_grid) {
-  if (n_kp < 0 || n_cams < 1 || !gp || !cell_ptr || (n_kp > 0 && (!kp_xy || !kp_cam || !cell_kp)))
-    return MCS_ERR_ARG;
-  const int ncell = n_cams * win::kCols * win::kRows;
-  std::vector<int32_t> cell(n_kp, -1), cnt(ncell + 1, 0);
-  for (int i = 0; i < n_kp; i++) {
-    const int c = kp_cam[i];
-    if (c < 0 || c >= n_cams) continue;
-    // PosInGrid: cvRound((kp.pt.x - mnMinX) * inv); float - int (mnMinX is an int) is a float
-    const float fx = kp_xy[2 * i] - (float)gp[4 * c], fy = kp_xy[2 * i + 1] - (float)gp[4 * c + 1];
-    const int px = cv_round((double)fx * gp[4 * c + 2]);
-    const int py = cv_round((double)fy * gp[4 * c + 3]);
-    if (px < 0 || px >= win::kCols || py < 0 || py >= win::kRows) continue;
-    cell[i] = (c * win::kCols + px) * win::kRows + py;
-    cnt[cell[i] + 1]++;
-  }
-  for (int k = 0; k < ncell; k++) cnt[k + 1] += cnt[k];
-  for (int k = 0; k <= ncell; k++) cell_ptr[k] = cnt[k];
-  for (int i = 0; i < n_kp; i++)     // keypoints in index order = push_back order (:180-181)
-    if (cell[i] >= 0) cell_kp[cnt[cell[i]]++] = i;
-  if (n_in_grid) *n_in_grid = cell_ptr[ncell];
-  return MCS_OK;
-}
 
 int mcs_window_search_device(const int32_t* d_cell_ptr, const int32_t* d_cell_kp,
                              const double* d_grid_params, int32_t n_cams, const float* d_kp_xy,
@@ -181,7 +139,8 @@ int mcs_window_search_device(const int32_t* d_cell_ptr, const int32_t* d_cell_kp
                              const uint8_t* d_q_desc, const uint8_t* d_q_mask,
                              int32_t* d_cand_ptr, int32_t* d_cand_kp, int32_t* d_cand_dist,
                              int64_t cap, int64_t* total, void* stream) {
-  if (!total || nq < 0 || n_cams < 1 || (bytes != 16 && bytes != 32 && bytes != 64)) return MCS_ERR_ARG;
+  if (!total || nq < 0 || n_cams < 1) return MCS_ERR_ARG;
+  if (int rc = host::check_desc_bytes(bytes, "window search")) return rc;
   if (!d_cand_ptr || (nq > 0 && (!d_q_xyr || !d_q_cam_lvl || !d_q_desc || !d_grid_params ||
                                  !d_cell_ptr))) return MCS_ERR_ARG;
   if ((d_q_mask == nullptr) != (d_kp_mask == nullptr)) {
@@ -212,66 +171,6 @@ int mcs_window_search_device(const int32_t* d_cell_ptr, const int32_t* d_cell_kp
   return MCS_OK;
 }
 
-int mcs_window_select(int32_t rule, int32_t nq, const int32_t* cand_ptr, const int32_t* cand_kp,
-                      const int32_t* cand_dist, const int32_t* kp_octave, int32_t n_kp,
-                      int32_t th, double nnratio, uint8_t* kp_assigned, int32_t* match,
-                      int32_t* n_matches) {
-  if (rule < 0 || rule > 3 || nq < 0 || n_kp < 0 || !cand_ptr || !match || !n_matches) return MCS_ERR_ARG;
-  if (rule != 2 && n_kp > 0 && !kp_assigned) return MCS_ERR_ARG;
-  if (rule == 0 && n_kp > 0 && !kp_octave) return MCS_ERR_ARG;
-  if (nq > 0 && cand_ptr[nq] > 0 && (!cand_kp || !cand_dist)) return MCS_ERR_ARG;
-  for (int q = 0; q < nq; q++) match[q] = -1;
-  int nm = 0;
-  if (rule == 2) {
-    // SearchForInitialization (:596-690): a train keypoint keeps the closest query so far
-    std::vector<int> matched_dist(n_kp, INT_MAX), m21(n_kp, -1);
-    for (int q = 0; q < nq; q++) {
-      int best = INT_MAX, best2 = INT_MAX, bi = -1;
-      for (int c = cand_ptr[q]; c < cand_ptr[q + 1]; c++) {
-        const int k = cand_kp[c], d = cand_dist[c];
-        if (matched_dist[k] <= d) continue;
-        if (d < best) { best2 = best; best = d; bi = k; }
-        else if (d < best2) best2 = d;
-      }
-      if (best <= th && best < (double)best2 * nnratio) {
-        if (m21[bi] >= 0) { match[m21[bi]] = -1; nm--; }
-        match[q] = bi;
-        m21[bi] = q;
-        matched_dist[bi] = best;
-        nm++;
-      }
-    }
-    *n_matches = nm;
-    return MCS_OK;
-  }
-  for (int q = 0; q < nq; q++) {
-    int best = INT_MAX, best2 = INT_MAX, bi = -1, lvl = -1, lvl2 = -1;
-    for (int c = cand_ptr[q]; c < cand_ptr[q + 1]; c++) {
-      const int k = cand_kp[c], d = cand_dist[c];
-      if (kp_assigned[k]) continue;
-      if (d < best) {
-        best2 = best; best = d;
-        lvl2 = lvl; lvl = rule == 0 ? kp_octave[k] : 0;
-        bi = k;
-      } else if (d < best2) {
-        lvl2 = rule == 0 ? kp_octave[k] : 0;
-        best2 = d;
-      }
-    }
-    bool accept;
-    if (rule == 0) accept = best <= th && !(lvl == lvl2 && best > nnratio * best2);   // :154-157
-    else if (rule == 1) accept = best <= th;                                          // :2078
-    else accept = best <= best2 * nnratio && best <= th;                              // :416
-    if (accept) {
-      kp_assigned[bi] = 1;
-      match[q] = bi;
-      nm++;
-    }
-  }
-  *n_matches = nm;
-  return MCS_OK;
-}
-
 int mcs_window_match(int32_t device, int32_t rule, const mcs_window_frame* f, int32_t nq,
                      const double* q_xyr, const int32_t* q_cam_lvl, const uint8_t* q_desc,
                      const uint8_t* q_mask, int32_t th, double nnratio, uint8_t* kp_assigned,
@@ -280,31 +179,26 @@ int mcs_window_match(int32_t device, int32_t rule, const mcs_window_frame* f, in
     return MCS_ERR_ARG;
   if (f->n_kp > 0 && (!f->kp_xy || !f->kp_cam || !f->kp_octave || !f->desc)) return MCS_ERR_ARG;
   if (nq > 0 && (!q_xyr || !q_cam_lvl || !q_desc)) return MCS_ERR_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("no HIP device visible (no CPU fallback)");
-    return MCS_ERR_NO_DEVICE;
-  }
-  if (device < 0 || device >= ndev) return MCS_ERR_ARG;
-  MCS_HIP_CHECK(hipSetDevice(device));
+  int rc = host::open_device(device, "window match");
+  if (rc) return rc;
   const int ncell = f->n_cams * win::kCols * win::kRows;
   std::vector<int32_t> cell_ptr(ncell + 1), cell_kp(std::max(1, f->n_kp));
-  int rc = mcs_frame_grid_build(f->kp_xy, f->kp_cam, f->n_kp, f->n_cams, f->grid_params,
+  rc = mcs_frame_grid_build(f->kp_xy, f->kp_cam, f->n_kp, f->n_cams, f->grid_params,
                                 cell_ptr.data(), cell_kp.data(), nullptr);
   if (rc) return rc;
   const size_t nk = (size_t)f->n_kp, nb = (size_t)f->bytes, nqs = (size_t)nq;
-  win::DevBufs B;
+  host::DevBufs B;
   const double* d_gp = B.up(f->grid_params, 4 * (size_t)f->n_cams);
   const int32_t* d_cptr = B.up(cell_ptr.data(), cell_ptr.size());
   const int32_t* d_ckp = B.up(cell_kp.data(), (size_t)cell_ptr[ncell]);
   const float* d_xy = B.up(f->kp_xy, 2 * nk);
   const int32_t* d_oct = B.up(f->kp_octave, nk);
   const uint8_t* d_desc = B.up(f->desc, nk * nb);
-  const uint8_t* d_mask = f->desc_mask ? B.up(f->desc_mask, nk * nb) : nullptr;
+  const uint8_t* d_mask = B.up(f->desc_mask, nk * nb);
   const double* d_q = B.up(q_xyr, 3 * nqs);
   const int32_t* d_ql = B.up(q_cam_lvl, 3 * nqs);
   const uint8_t* d_qd = B.up(q_desc, nqs * nb);
-  const uint8_t* d_qm = q_mask ? B.up(q_mask, nqs * nb) : nullptr;
+  const uint8_t* d_qm = B.up(q_mask, nqs * nb);
   int32_t* d_cp = B.alloc<int32_t>(nqs + 1);
   int64_t cap = std::max<int64_t>(1024, 32 * (int64_t)nq), total = 0;
   int32_t* d_ck = B.alloc<int32_t>((size_t)cap);
@@ -322,11 +216,10 @@ int mcs_window_match(int32_t device, int32_t rule, const mcs_window_frame* f, in
   }
   if (rc) return rc;
   std::vector<int32_t> cp(nqs + 1), ck(std::max<int64_t>(1, total)), cd(std::max<int64_t>(1, total));
-  MCS_HIP_CHECK(hipMemcpy(cp.data(), d_cp, 4 * (nqs + 1), hipMemcpyDeviceToHost));
-  if (total > 0) {
-    MCS_HIP_CHECK(hipMemcpy(ck.data(), d_ck, 4 * (size_t)total, hipMemcpyDeviceToHost));
-    MCS_HIP_CHECK(hipMemcpy(cd.data(), d_cd, 4 * (size_t)total, hipMemcpyDeviceToHost));
-  }
+  B.down(cp.data(), d_cp, nqs + 1);
+  B.down(ck.data(), d_ck, (size_t)total);
+  B.down(cd.data(), d_cd, (size_t)total);
+  if (B.err != hipSuccess) { set_hip_error(B.err, "window match download", __FILE__, __LINE__); return MCS_ERR_HIP; }
   std::vector<uint8_t> fresh;
   if (!kp_assigned) { fresh.assign(std::max(1, f->n_kp), 0); kp_assigned = fresh.data(); }
   return mcs_window_select(rule, nq, cp.data(), ck.data(), cd.data(), f->kp_octave, f->n_kp, th,

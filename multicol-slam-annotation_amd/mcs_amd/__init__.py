@@ -231,6 +231,27 @@ def _check(rc):
         raise McsError(rc, lib().mcs_last_error().decode(errors="replace"))
 
 
+class _Workspace:
+    """A device workspace handle: `create`(device, *args, &handle) now, `destroy`(handle) at
+    close() or when collected.  create / destroy are symbol names of the library."""
+
+    def __init__(self, create, destroy, device, *args):
+        h = ctypes.c_void_p()
+        _check(getattr(lib(), create)(int(device), *(int(a) for a in args), ctypes.byref(h)))
+        self._h, self._destroy, self.device = h, destroy, device
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(lib(), self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def device_count():
     return int(lib().mcs_device_count())
 

@@ -20,7 +20,7 @@ import ctypes
 
 import numpy as np
 
-from . import McsError, _check, lib
+from . import McsError, _Workspace, _check, lib
 
 
 class BowSet(ctypes.Structure):
@@ -117,25 +117,12 @@ def device_set(p, device=0):
     return s, keep
 
 
-class Workspace:
+class Workspace(_Workspace):
     """mcs_bow_workspace: device scratch for frames of <= max_kp keypoints and batches of
     <= max_candidates candidates."""
 
     def __init__(self, max_kp, max_candidates, device=0):
-        h = ctypes.c_void_p()
-        _check(lib().mcs_bow_workspace_create(int(device), int(max_kp), int(max_candidates), ctypes.byref(h)))
-        self._h, self.device = h, device
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().mcs_bow_workspace_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__("mcs_bow_workspace_create", "mcs_bow_workspace_destroy", device, max_kp, max_candidates)
 
 
 def _stream(device):

@@ -22,7 +22,7 @@ import ctypes
 
 import numpy as np
 
-from . import McsError, _check, lib
+from . import McsError, _Workspace, _check, lib
 from .window import GRID_COLS, GRID_ROWS, grid_build
 
 USE_DISTANCE = 1          # MCS_FUSE_USE_DISTANCE
@@ -161,24 +161,11 @@ def device_sets(pt, pq, device=0):
     return ts, qs, (k1, k2)
 
 
-class Workspace:
+class Workspace(_Workspace):
     """mcs_fuse_workspace: device scratch for batches of <= max_targets targets."""
 
     def __init__(self, max_targets, device=0):
-        h = ctypes.c_void_p()
-        _check(lib().mcs_fuse_workspace_create(int(device), int(max_targets), ctypes.byref(h)))
-        self._h, self.device = h, device
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().mcs_fuse_workspace_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__("mcs_fuse_workspace_create", "mcs_fuse_workspace_destroy", device, max_targets)
 
 
 def fuse_device(ws, rule, tset, qset, th, th_low, flags=0, q_skip=None, device=0, out=None):

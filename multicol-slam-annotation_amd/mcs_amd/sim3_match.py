@@ -19,7 +19,7 @@ import ctypes
 
 import numpy as np
 
-from . import McsError, _check, lib
+from . import McsError, _Workspace, _check, lib
 from .fuse import _T_DTYPES, _T_INTS, FuseTargets, _device, _host, pack_targets
 
 
@@ -63,24 +63,11 @@ def device_sets(pk, pp, device=0):
     return ks, ps, (a, b)
 
 
-class Workspace:
+class Workspace(_Workspace):
     """mcs_sim3_workspace: device scratch for <= max_targets candidates of <= max_kp keypoints."""
 
     def __init__(self, max_targets, max_kp, device=0):
-        h = ctypes.c_void_p()
-        _check(lib().mcs_sim3_workspace_create(int(device), int(max_targets), int(max_kp), ctypes.byref(h)))
-        self._h, self.device = h, device
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().mcs_sim3_workspace_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__("mcs_sim3_workspace_create", "mcs_sim3_workspace_destroy", device, max_targets, max_kp)
 
 
 def search_by_sim3_device(ws, k1, p1, k2, p2, active1, active2, s12, R12, t12, th, th_high, device=0, out=None):

@@ -19,7 +19,7 @@ import ctypes
 
 import numpy as np
 
-from . import McsError, _check, lib
+from . import McsError, _Workspace, _check, lib
 from .fuse import pack_targets
 from .sim3_match import device_sets, host_sets, pack_points
 
@@ -95,26 +95,13 @@ def _torch_struct(struct, shapes, dev, given=None, skip=()):
     return s, ts
 
 
-class Workspace:
+class Workspace(_Workspace):
     """mcs_sim3_solver_workspace: scratch for <= max_targets candidates of <= max_kp correspondences
     and calls of <= max_its_cap iterations."""
 
     def __init__(self, max_targets, max_kp, max_its_cap, device=0):
-        h = ctypes.c_void_p()
-        _check(lib().mcs_sim3_solver_workspace_create(int(device), int(max_targets), int(max_kp), int(max_its_cap),
-                                                      ctypes.byref(h)))
-        self._h, self.device = h, device
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().mcs_sim3_solver_workspace_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__("mcs_sim3_solver_workspace_create", "mcs_sim3_solver_workspace_destroy", device,
+                         max_targets, max_kp, max_its_cap)
 
 
 def pack_call(rig, kf1, pts1, kf2s, pts2s, matches12, ok1, ok2s, first1, first2s, nbytes=None):
