@@ -88,7 +88,9 @@ int mcs_search_for_triangulation_raw_masked(const uint8_t* desc1, const uint8_t*
  * (src/cLocalMapping.cpp:223-266 -> src/cORBmatcher.cpp:968-1156): the same match list as
  * the two host entries above, on device buffers and stream-ordered (no host synchronisation),
  * so a caller keeps KF descriptors, rays and has-map-point flags resident and runs one call per
- * neighbour keyframe, updating d_has_mp1 between calls as the reference's triangulation does.
+ * neighbour keyframe, updating d_has_mp1 between calls as the reference's triangulation does
+ * (mcs_create_new_map_points_device of mcs_newpoints.h runs that loop: search, triangulation and
+ * the flag update per neighbour on one stream).
  * d_mask1 / d_mask2: both null (ORB, DescriptorDistance64) or both set (mdBRIEF, ...Masked).
  * d_E [ncams][ncams][9] (mcs_compute_e_rig).  Out: d_matches12[n1] (-1 = none), *d_n_matches.
  * Keypoints whose camera lies outside [0, ncams) never match (the host entries reject them).
@@ -115,6 +117,11 @@ int mcs_search_for_triangulation_raw_device(mcs_tri_workspace* ws, const uint8_t
  * Host math in the reference's cv::Matx operation order. */
 int mcs_compute_e_rig(const double* mt1, const double* mt2, const double* mc, int32_t ncams,
                       double* E);
+
+/* The same from the 4 x 4 matrices themselves, for callers that hold Get_M_t() and M_c (the
+ * resident keyframe form mcs_fuse_targets): m_t1, m_t2 [16], m_c [ncams][16], row-major. */
+int mcs_compute_e_rig_hom(const double* m_t1, const double* m_t2, const double* m_c, int32_t ncams,
+                          double* E);
 
 /* CheckDistEpipolarLine(ray1, ray2, E12, thresh) (src/misc.cpp:54-70): 1 = passes (squared
  * epipolar distance < thresh), 0 = fails (or den == 0), < 0 = argument error.  The check the

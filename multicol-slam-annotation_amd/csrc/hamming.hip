@@ -1259,6 +1259,21 @@ int mcs_compute_e_rig(const double* mt1, const double* mt2, const double* mc, in
   return MCS_OK;
 }
 
+int mcs_compute_e_rig_hom(const double* m_t1, const double* m_t2, const double* m_c, int32_t ncams,
+                          double* E) {
+  if (!m_t1 || !m_t2 || !m_c || !E || ncams <= 0) { set_error("compute_e_rig_hom: bad arguments"); return MCS_ERR_ARG; }
+  double M[16], inv1[16];
+  for (int i = 0; i < ncams; i++) {
+    host_matmul(m_t1, m_c + 16 * i, M, 4, 4, 4);
+    host_inv_mat(M, inv1);
+    for (int j = 0; j < ncams; j++) {
+      host_matmul(m_t2, m_c + 16 * j, M, 4, 4, 4);
+      host_compute_e(inv1, M, E + 9 * ((size_t)i * ncams + j));
+    }
+  }
+  return MCS_OK;
+}
+
 int mcs_check_dist_epipolar_line(const double* ray1, const double* ray2, const double* E12,
                                  double thresh) {
   if (!ray1 || !ray2 || !E12) { set_error("check_dist_epipolar_line: null argument"); return MCS_ERR_ARG; }

@@ -3,6 +3,7 @@
 //   cMapPoint::ComputeDistinctiveDescriptors  src/cMapPoint.cpp:297-390 (median: include/misc.h:97-105)
 //   cMapPoint::UpdateNormalAndDepth           src/cMapPoint.cpp:453-496
 #include "common.hpp"
+#include "mappoint_math.hpp"
 #include "../../include/mcs_mappoint.h"
 
 namespace mcs {
@@ -102,17 +103,7 @@ __global__ __launch_bounds__(256) void k_distinctive(const uint8_t* __restrict__
   }
 }
 
-// cv::norm of a Vec3d: sqrt of the in-order sum of squares (normL2Sqr)
-__device__ __forceinline__ double norm3(double x, double y, double z) {
-  double s = 0.0;
-  s = __dadd_rn(s, __dmul_rn(x, x));
-  s = __dadd_rn(s, __dmul_rn(y, y));
-  s = __dadd_rn(s, __dmul_rn(z, z));
-  return __dsqrt_rn(s);
-}
-
-// one thread per point, the reference's cv::Vec3d arithmetic: v / a is v * (1. / a)
-// (Vec operator/ -> Matx_ScaleOp), sums in observation order
+// one thread per point; the arithmetic is mappoint_math.hpp's (shared with new_points.hip)
 __global__ __launch_bounds__(256) void k_normal_depth(const double* __restrict__ pts, int n,
                                                       const int32_t* __restrict__ obs_ptr,
                                                       const int32_t* __restrict__ obs_kf,
@@ -131,25 +122,14 @@ __global__ __launch_bounds__(256) void k_normal_depth(const double* __restrict__
   double nx = 0.0, ny = 0.0, nz = 0.0;
   int cnt = 0;
   for (int q = q0; q < q1; q++) {
-    const double* O = kf_c + 3 * (int64_t)obs_kf[q];
-    const double ax = __dsub_rn(X, O[0]), ay = __dsub_rn(Y, O[1]), az = __dsub_rn(Z, O[2]);
-    const double ia = __ddiv_rn(1.0, norm3(ax, ay, az));
-    nx = __dadd_rn(nx, __dmul_rn(ax, ia));
-    ny = __dadd_rn(ny, __dmul_rn(ay, ia));
-    nz = __dadd_rn(nz, __dmul_rn(az, ia));
+    mpt::add_view_dir(X, Y, Z, kf_c + 3 * (int64_t)obs_kf[q], nx, ny, nz);
     ++cnt;
   }
-  const double* R = kf_c + 3 * (int64_t)ref_kf[p];
-  const double dist = norm3(__dsub_rn(X, R[0]), __dsub_rn(Y, R[1]), __dsub_rn(Z, R[2]));
+  const double dist = mpt::ref_dist(X, Y, Z, kf_c + 3 * (int64_t)ref_kf[p]);
   int level = ref_level[p];
   if (level < 0) level = 1;
-  const double sf = scale[level];
-  dmin[p] = __ddiv_rn(__dmul_rn(__ddiv_rn(1.0, sf), dist), sf);
-  dmax[p] = __dmul_rn(__dmul_rn(sf, dist), scale[nlev - 1 - level]);
-  const double in = __ddiv_rn(1.0, (double)cnt);
-  normal[3 * p] = __dmul_rn(nx, in);
-  normal[3 * p + 1] = __dmul_rn(ny, in);
-  normal[3 * p + 2] = __dmul_rn(nz, in);
+  mpt::dist_range(dist, scale, nlev, level, dmin[p], dmax[p]);
+  mpt::mean_dir(nx, ny, nz, cnt, normal + 3 * (int64_t)p);
 }
 
 template <int NW>

@@ -13,10 +13,13 @@
 //                                                     mcs::GlobalBA::run(map, poseOnly, pbStopFlag)
 //   cOptimizer::PoseOptimization (cOptimizer.h:67-69) mcs::PoseOptimizer::run(frame, inliers,
 //                                                                        huberMultiplier)
+//   cLocalMapping::CreateNewMapPoints (src/cLocalMapping.cpp:224-386)
+//                                                     mcs::CreateNewMapPoints(rig, cur, neighbours, ...)
 //
 // cv::KeyPoint-compatible: mcs_keypoint has cv::KeyPoint's field order and size (28 B), so a
 // std::vector<mcs_keypoint> can be copied into std::vector<cv::KeyPoint> member-wise.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cmath>
 #include <cstring>
@@ -28,6 +31,7 @@
 #include "../../include/mcs_ba.h"
 #include "../../include/mcs_extractor.h"
 #include "../../include/mcs_matcher.h"
+#include "../../include/mcs_newpoints.h"
 
 namespace mcs {
 
@@ -729,5 +733,78 @@ class Sim3Solver {
   int32_t its_ = 0, best_ = 0, max_its_ = 0;
   double s_ = 0, R_[9] = {0}, t_[3] = {0}, T_[16] = {0};
 };
+
+// cLocalMapping::CreateNewMapPoints (src/cLocalMapping.cpp:224-386) at its call site (:99): the
+// neighbour loop (SearchForTriangulationRaw, then the per-match loop :272-382) in one device call
+// (mcs_create_new_map_points).  The caller does what needs the map: the neighbours
+// (GetBestCovisibilityKeyFrames(5)), `skip` = the ratioBaselineDepth < 0.01 gate (:248-256) per
+// neighbour, `kf2_first` = whether the neighbour precedes the current keyframe in the new point's
+// std::map<cMultiKeyFrame*, ...> (pointer order: pKF2 < mpCurrentMultiKeyFrame), and afterwards
+// `new cMapPoint`, AddObservation, AddMapPoint and mpMap->AddMapPoint for every returned point.
+struct NewMapPoint {
+  int neighbour = 0, idx1 = 0, idx2 = 0;   // index into `neighbours`, keypoint of cur, keypoint of the neighbour
+  double pos[3] = {0, 0, 0}, normal[3] = {0, 0, 0}, minDist = 0, maxDist = 0;   // mWorldPos, mNormalVector, mf{Min,Max}Distance
+  std::vector<uint8_t> desc, mask;         // mDescriptor, mDescriptorMask (empty without masks)
+};
+
+// has_mp [1 + T]: nonzero = the keypoint holds a map point (mvpMapPoints[i] != NULL), the current
+// keyframe first; updated as AddMapPoint does (:370-371).  TH_LOW = the matcher's TH_LOW_ (2 * featDim,
+// or featDim with masks); rays must be filled.  Keypoints must lie in cameras [0, n_cams).
+inline std::vector<NewMapPoint> CreateNewMapPoints(const FuseRig& rig, const FuseKeyFrame& cur,
+                                                   const std::vector<const FuseKeyFrame*>& neighbours,
+                                                   std::vector<std::vector<uint8_t>*>& has_mp,
+                                                   const std::vector<uint8_t>& skip,
+                                                   const std::vector<uint8_t>& kf2_first, int featDim, int TH_LOW,
+                                                   double epi_thresh = 1e-2, int device = 0) {
+  const int T = (int)neighbours.size(), C = rig.n_cams;
+  if ((int)skip.size() != T || (int)kf2_first.size() != T || (int)has_mp.size() != T + 1)
+    throw std::invalid_argument("CreateNewMapPoints: skip, kf2_first and has_mp must fit the neighbours");
+  const bool masked = !cur.mask.empty();
+  std::vector<int32_t> off(1, 0), oct, cam;
+  std::vector<float> xy;
+  std::vector<uint8_t> desc, mask, has;
+  std::vector<double> rays, m_t, E((size_t)T * C * C * 9 + 1);
+  for (int t = 0; t <= T; t++) {
+    const FuseKeyFrame& k = t ? *neighbours[t - 1] : cur;
+    const size_t n = k.kp_octave.size();
+    if (masked != !k.mask.empty() || has_mp[t]->size() != n || k.rays.size() != 3 * n)
+      throw std::invalid_argument("CreateNewMapPoints: masks for every keyframe or none; has_mp and rays per keypoint");
+    off.push_back(off.back() + (int32_t)n);
+    xy.insert(xy.end(), k.kp_xy.begin(), k.kp_xy.end());
+    oct.insert(oct.end(), k.kp_octave.begin(), k.kp_octave.end());
+    cam.insert(cam.end(), k.kp_cam.begin(), k.kp_cam.end());
+    desc.insert(desc.end(), k.desc.begin(), k.desc.end());
+    mask.insert(mask.end(), k.mask.begin(), k.mask.end());
+    rays.insert(rays.end(), k.rays.begin(), k.rays.end());
+    has.insert(has.end(), has_mp[t]->begin(), has_mp[t]->end());
+    m_t.insert(m_t.end(), k.m_t, k.m_t + 16);
+    if (t)   // Es[i][j] of SearchForTriangulationRaw (src/cORBmatcher.cpp:985-998)
+      check(mcs_compute_e_rig_hom(cur.m_t, k.m_t, rig.m_c.data(), C, &E[(size_t)(t - 1) * C * C * 9]), "mcs_compute_e_rig_hom");
+  }
+  mcs_fuse_targets kfs{T + 1, off.back(), C, featDim, (int32_t)rig.scale.size(), rig.mirror_w, rig.mirror_h,
+                       off.data(), xy.data(), oct.data(), cam.data(), desc.data(), masked ? mask.data() : nullptr,
+                       rays.data(), m_t.data(), rig.m_c.data(), rig.cam.data(), nullptr, nullptr, rig.scale.data(),
+                       nullptr, nullptr};
+  const size_t n1 = cur.kp_octave.size(), cap = n1 * (size_t)(T > 0 ? T : 1) + 1, nb = (size_t)featDim;
+  int32_t count = 0;
+  std::vector<int32_t> kp1(cap), kp2(cap), nbr(cap);
+  std::vector<double> pos(3 * cap), nrm(3 * cap), dmin(cap), dmax(cap);
+  std::vector<uint8_t> od(cap * nb), om(masked ? cap * nb : 1);
+  mcs_new_points out{(int32_t)cap, &count, kp1.data(), kp2.data(), nbr.data(), pos.data(), nrm.data(), dmin.data(),
+                     dmax.data(), od.data(), masked ? om.data() : nullptr};
+  check(mcs_create_new_map_points(device, &kfs, skip.data(), kf2_first.data(), E.data(), has.data(), TH_LOW, epi_thresh,
+                                  nullptr, nullptr, &out), "mcs_create_new_map_points");
+  for (int t = 0; t <= T; t++) std::copy(has.begin() + off[t], has.begin() + off[t + 1], has_mp[t]->begin());
+  std::vector<NewMapPoint> pts((size_t)count);
+  for (int p = 0; p < count; p++) {
+    NewMapPoint& q = pts[p];
+    q.neighbour = nbr[p]; q.idx1 = kp1[p]; q.idx2 = kp2[p];
+    for (int j = 0; j < 3; j++) { q.pos[j] = pos[3 * (size_t)p + j]; q.normal[j] = nrm[3 * (size_t)p + j]; }
+    q.minDist = dmin[p]; q.maxDist = dmax[p];
+    q.desc.assign(od.begin() + (size_t)p * nb, od.begin() + (size_t)(p + 1) * nb);
+    if (masked) q.mask.assign(om.begin() + (size_t)p * nb, om.begin() + (size_t)(p + 1) * nb);
+  }
+  return pts;
+}
 
 }  // namespace mcs

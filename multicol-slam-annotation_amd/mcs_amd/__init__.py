@@ -145,6 +145,7 @@ SIGNATURES = {
     "mcs_search_for_triangulation_raw": (ctypes.c_int, [_P, _P, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _P, _I32, _I32, ctypes.c_double, _P, _P]),
     "mcs_search_for_triangulation_raw_masked": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _I32, _I32, _P, _I32, _I32, ctypes.c_double, _P, _P]),
     "mcs_compute_e_rig": (ctypes.c_int, [_P, _P, _P, _I32, _P]),
+    "mcs_compute_e_rig_hom": (ctypes.c_int, [_P, _P, _P, _I32, _P]),
     "mcs_ba_point_block_eval": (ctypes.c_int, [_I32, _P, ctypes.c_double, _P, _P, _I32, _P, _P, _P]),
     "mcs_tri_workspace_create": (ctypes.c_int, [_I32, _I32, _I32, _P]),
     "mcs_tri_workspace_destroy": (None, [_P]),
@@ -184,6 +185,12 @@ SIGNATURES = {
     "mcs_sim3_solver_iterate_device": (ctypes.c_int, [_P, _P, _P, _I32, ctypes.c_double, _I32, _I32, _I32, _P, _P]),
     "mcs_sim3_solver_active_device": (ctypes.c_int, [_P] * 10),
     "mcs_sim3_solver": (ctypes.c_int, [_I32] + [_P] * 11 + [_I32, ctypes.c_double, _I32, _I32, _I32] + [_P] * 6),
+    # CreateNewMapPoints (include/mcs_newpoints.h; wrappers in mcs_amd/new_points.py)
+    "mcs_newpts_workspace_create": (ctypes.c_int, [_I32, _I32, _P]),
+    "mcs_newpts_workspace_destroy": (None, [_P]),
+    "mcs_new_points_pair_device": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P]),
+    "mcs_create_new_map_points_device": (ctypes.c_int, [_P] * 8 + [_I32, ctypes.c_double] + [_P] * 4),
+    "mcs_create_new_map_points": (ctypes.c_int, [_I32] + [_P] * 5 + [_I32, ctypes.c_double] + [_P] * 3),
     # DBoW2 vocabulary (include/mcs_vocab.h)
     "mcs_vocab_create": (_I32, [_I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _P, _I32, _P]),
     "mcs_vocab_destroy": (_I32, [_P]),
