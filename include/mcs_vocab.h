@@ -64,6 +64,20 @@ int mcs_vocab_transform(const mcs_vocab* voc, const uint8_t* desc, int32_t n, in
                         uint32_t* bow_word, double* bow_value, int32_t* bow_n, uint32_t* fv_node,
                         int32_t* fv_ptr, uint32_t* fv_feat, int32_t* fv_n);
 
+/* The BowVector of transform(features, BowVector&, FeatureVector&, levelsup)
+ * (TemplatedVocabulary.h:1126-1196, BowVector.cpp:34-86) from the per-descriptor d_word / d_weight
+ * [n] that mcs_vocab_transform_words_device writes, without leaving the device: d_bow_word
+ * ascending and unique, d_bow_value (capacity n each) and the device count *d_bow_n.  Bit for bit
+ * what mcs_vocab_transform returns in bow_word / bow_value / bow_n: stopped words (weight <= 0)
+ * are dropped, a word seen c times holds w + w + ... + w added one at a time (TF_IDF / TF), and
+ * the norm is the sum in ascending word order, added one after the other.  ws is the
+ * mcs_bow_workspace of mcs_matcher.h (n <= its max_kp; the FeatureVector's sort storage is
+ * reused).  Stream-ordered, no host synchronisation, no allocation. */
+struct mcs_bow_workspace;
+int mcs_bow_vector_device(struct mcs_bow_workspace* ws, const mcs_vocab* voc, const uint32_t* d_word,
+                          const double* d_weight, int32_t n, uint32_t* d_bow_word,
+                          double* d_bow_value, int32_t* d_bow_n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

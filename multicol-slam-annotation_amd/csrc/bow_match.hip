@@ -8,6 +8,7 @@
 #include "host_util.hpp"
 #include "ham_dist.hpp"
 #include "../../include/mcs_matcher.h"
+#include "../../include/mcs_vocab.h"
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 #include <algorithm>
@@ -384,6 +385,59 @@ __global__ void k_fv_keys(const uint32_t* __restrict__ node, const double* __res
   val[i] = (uint32_t)i;
 }
 
+// ---- device BowVector: (word, weight) per descriptor -> ascending unique words with values.
+// The words go through the FeatureVector's sort / flag / scan / emit (word in place of node:
+// seg[j] .. seg[j+1] are the descriptors of word j in feature order); the values follow
+// mcs_vocab_transform's evaluation order to the bit.
+// addWeight (TF_IDF / TF): the first weight, then one `+= w` per further occurrence, in feature
+// order -- not count * w.  addIfNotExist (IDF / BINARY): the first weight.
+__global__ void k_bow_values(const int32_t* __restrict__ seg, const uint32_t* __restrict__ feat,
+                             const double* __restrict__ weight, const int32_t* __restrict__ bow_n, int n,
+                             int tf, double* __restrict__ value) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= min(*bow_n, n)) return;
+  const int b = max(seg[j], 0), e = min(seg[j + 1], n);
+  if (b >= e) { value[j] = 0.0; return; }
+  double v = weight[feat[b]];
+  if (tf)
+    for (int i = b + 1; i < e; i++) v += weight[feat[i]];
+  value[j] = v;
+}
+
+// BowVector::normalize (BowVector.cpp:66-86) / the TF division of transform (:1166-1172).  The
+// norm is the serial sum in ascending word order that std::map iteration gives the reference: ONE
+// lane adds the values one after the other, from LDS chunks the block stages.  This is deliberate:
+// a tree reduction would be faster and would change the last bits of every value.
+constexpr int kBowNormChunk = 2048;
+__global__ __launch_bounds__(256) void k_bow_normalize(const int32_t* __restrict__ bow_n, int n, int mode,
+                                                      double* __restrict__ value) {
+  __shared__ double s_v[kBowNormChunk];
+  __shared__ double s_norm;
+  const int m = min(max(*bow_n, 0), n);
+  if (mode == 0 || m == 0) return;
+  if (mode == 3) {   // TF weighting without a normalising scoring: v /= size
+    const double nd = (double)m;
+    for (int i = threadIdx.x; i < m; i += 256) value[i] /= nd;
+    return;
+  }
+  double norm = 0.0;
+  for (int c = 0; c < m; c += kBowNormChunk) {
+    const int len = min(kBowNormChunk, m - c);
+    for (int i = threadIdx.x; i < len; i += 256) s_v[i] = value[c + i];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      if (mode == 1) for (int i = 0; i < len; i++) norm += fabs(s_v[i]);
+      else for (int i = 0; i < len; i++) norm += s_v[i] * s_v[i];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) s_norm = mode == 2 ? sqrt(norm) : norm;
+  __syncthreads();
+  const double nrm = s_norm;
+  if (nrm > 0.0)
+    for (int i = threadIdx.x; i < m; i += 256) value[i] /= nrm;
+}
+
 __global__ void k_fv_flag(const uint32_t* __restrict__ key, int n, int32_t* __restrict__ flag) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i > n) return;
@@ -416,6 +470,8 @@ struct mcs_bow_workspace {
   uint32_t* key_in = nullptr;   // [max_kp] each
   uint32_t* key_out = nullptr;
   uint32_t* val_in = nullptr;
+  uint32_t* val_out = nullptr;  // [max_kp]      the BowVector's sorted descriptor indices
+  int32_t* seg = nullptr;       // [max_kp + 1]  and its word segments
   int32_t* flag = nullptr;      // [max_kp + 1]
   int32_t* pos = nullptr;       // [max_kp + 1]
   void* tmp = nullptr; size_t tmp_bytes = 0;
@@ -643,6 +699,8 @@ static int bow_ws_create(int32_t device, int32_t max_kp, int32_t max_candidates,
   if (e == hipSuccess) e = hipMalloc((void**)&w->key_in, 4 * n);
   if (e == hipSuccess) e = hipMalloc((void**)&w->key_out, 4 * n);
   if (e == hipSuccess) e = hipMalloc((void**)&w->val_in, 4 * n);
+  if (e == hipSuccess) e = hipMalloc((void**)&w->val_out, 4 * n);
+  if (e == hipSuccess) e = hipMalloc((void**)&w->seg, 4 * (n + 1));
   if (e == hipSuccess) e = hipMalloc((void**)&w->flag, 4 * (n + 1));
   if (e == hipSuccess) e = hipMalloc((void**)&w->pos, 4 * (n + 1));
   size_t b_scan = 0, b_sort = 0;
@@ -672,7 +730,8 @@ int mcs_bow_workspace_create(int32_t device, int32_t max_kp, int32_t max_candida
 void mcs_bow_workspace_destroy(mcs_bow_workspace* w) {
   if (!w) return;
   (void)hipSetDevice(w->device);
-  void* bufs[] = {w->hist, w->keep, w->cand, w->cnt, w->key_in, w->key_out, w->val_in, w->flag, w->pos, w->tmp};
+  void* bufs[] = {w->hist, w->keep, w->cand, w->cnt, w->key_in, w->key_out, w->val_in, w->val_out, w->seg,
+                  w->flag, w->pos, w->tmp};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   delete w;
@@ -708,6 +767,48 @@ int mcs_feature_vector_device(mcs_bow_workspace* ws, const uint32_t* d_node, con
   MCS_HIP_CHECK(rocprim::exclusive_scan(ws->tmp, b, ws->flag, ws->pos, 0, (size_t)n + 1, rocprim::plus<int32_t>(), st));
   hipLaunchKernelGGL(k_fv_emit, dim3(nb), dim3(256), 0, st, ws->key_out, ws->flag, ws->pos, n, d_fv_node, d_fv_ptr,
                      d_fv_n);
+  MCS_HIP_CHECK(hipGetLastError());
+  return MCS_OK;
+}
+
+int mcs_bow_vector_device(mcs_bow_workspace* ws, const mcs_vocab* voc, const uint32_t* d_word,
+                          const double* d_weight, int32_t n, uint32_t* d_bow_word, double* d_bow_value,
+                          int32_t* d_bow_n, void* stream) {
+  int32_t info[6];
+  if (!ws || !voc || n < 0 || !d_bow_n || (n > 0 && (!d_word || !d_weight || !d_bow_word || !d_bow_value)) ||
+      mcs_vocab_info(voc, info) != MCS_OK) {
+    set_error("bow_vector_device: bad arguments");
+    return MCS_ERR_ARG;
+  }
+  if (n > ws->max_kp) { set_error("bow_vector_device: n above the workspace's max_kp"); return MCS_ERR_ARG; }
+  MCS_HIP_CHECK(hipSetDevice(ws->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (n == 0 || info[5] == 0) {   // v.clear(); an empty vocabulary returns at once (:1133-1138)
+    MCS_HIP_CHECK(hipMemsetAsync(d_bow_n, 0, 4, st));
+    return MCS_OK;
+  }
+  const int nb = (n + 1 + 255) / 256;
+  hipLaunchKernelGGL(k_fv_keys, dim3(nb), dim3(256), 0, st, d_word, d_weight, n, ws->key_in, ws->val_in);
+  // stable (LSD radix sort): the occurrences of one word stay in feature order
+  size_t need = 0;
+  MCS_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, need, ws->key_in, ws->key_out, ws->val_in, ws->val_out, (size_t)n,
+                                          0, 32, st));
+  if (need > ws->tmp_bytes) { set_error("bow_vector_device: sort storage above the workspace"); return MCS_ERR_CAPACITY; }
+  size_t b = ws->tmp_bytes;
+  MCS_HIP_CHECK(rocprim::radix_sort_pairs(ws->tmp, b, ws->key_in, ws->key_out, ws->val_in, ws->val_out, (size_t)n,
+                                          0, 32, st));
+  hipLaunchKernelGGL(k_fv_flag, dim3(nb), dim3(256), 0, st, ws->key_out, n, ws->flag);
+  b = ws->tmp_bytes;
+  MCS_HIP_CHECK(rocprim::exclusive_scan(ws->tmp, b, ws->flag, ws->pos, 0, (size_t)n + 1, rocprim::plus<int32_t>(), st));
+  hipLaunchKernelGGL(k_fv_emit, dim3(nb), dim3(256), 0, st, ws->key_out, ws->flag, ws->pos, n, d_bow_word, ws->seg,
+                     d_bow_n);
+  const int scoring = info[2], weighting = info[3];
+  const bool tf = weighting == 0 || weighting == 1;
+  // mustNormalize (ScoringObject.h:74-89): L2 scoring with L2, DOT_PRODUCT not at all, the rest L1
+  const int mode = scoring == 5 ? (tf ? 3 : 0) : scoring == 1 ? 2 : 1;
+  hipLaunchKernelGGL(k_bow_values, dim3(nb), dim3(256), 0, st, ws->seg, ws->val_out, d_weight, d_bow_n, n,
+                     tf ? 1 : 0, d_bow_value);
+  hipLaunchKernelGGL(k_bow_normalize, dim3(1), dim3(256), 0, st, d_bow_n, n, mode, d_bow_value);
   MCS_HIP_CHECK(hipGetLastError());
   return MCS_OK;
 }

@@ -15,6 +15,9 @@
 //                                                                        huberMultiplier)
 //   cLocalMapping::CreateNewMapPoints (src/cLocalMapping.cpp:224-386)
 //                                                     mcs::CreateNewMapPoints(rig, cur, neighbours, ...)
+//   cMultiKeyFrameDatabase (src/cMultiKeyFrameDatabase.cpp:43-340)
+//                                                     mcs::KeyFrameDatabase<cMultiKeyFrame>: add, erase, clear,
+//                                                     DetectLoopCandidates, DetectRelocalisationCandidates, MinScore
 //
 // cv::KeyPoint-compatible: mcs_keypoint has cv::KeyPoint's field order and size (28 B), so a
 // std::vector<mcs_keypoint> can be copied into std::vector<cv::KeyPoint> member-wise.
@@ -26,10 +29,12 @@
 #include <random>
 #include <stdexcept>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/mcs_ba.h"
 #include "../../include/mcs_extractor.h"
+#include "../../include/mcs_kfdb.h"
 #include "../../include/mcs_matcher.h"
 #include "../../include/mcs_newpoints.h"
 
@@ -806,5 +811,155 @@ inline std::vector<NewMapPoint> CreateNewMapPoints(const FuseRig& rig, const Fus
   }
   return pts;
 }
+
+// ---- cMultiKeyFrameDatabase (src/cMultiKeyFrameDatabase.cpp) on mcs_kfdb -----------------------
+// The device database names a keyframe by its slot (the add sequence number); the caller's code
+// names it by pointer.  KfSlots is that bookkeeping: pointer -> slot for every keyframe ever added
+// (an erased keyframe keeps its slot: it can still be somebody's neighbour and can still be
+// returned as pBestKF, as the reference's object stays alive), slot -> pointer for the results.
+template <class KF>
+class KfSlots {
+ public:
+  // the slot the next add receives
+  int32_t next() const { return (int32_t)kf_.size(); }
+  // records pKF at `slot` (the value mcs_kfdb_add returned); a pointer added again gets the new slot
+  void bind(const KF* pKF, int32_t slot) {
+    if (slot != next()) throw std::logic_error("KfSlots: slots are handed out in sequence");
+    kf_.push_back(pKF);
+    alive_.push_back(1);
+    map_[pKF] = slot;
+  }
+  // -1 when pKF was never added
+  int32_t slot(const KF* pKF) const {
+    const auto it = map_.find(pKF);
+    return it == map_.end() ? -1 : it->second;
+  }
+  const KF* kf(int32_t slot) const { return slot >= 0 && slot < next() ? kf_[slot] : nullptr; }
+  bool alive(int32_t slot) const { return slot >= 0 && slot < next() && alive_[slot]; }
+  // the slot to erase, or -1 when pKF is not in the database (erase of an absent keyframe is a no-op, :52-73)
+  int32_t erase(const KF* pKF) {
+    const int32_t s = slot(pKF);
+    if (!alive(s)) return -1;
+    alive_[s] = 0;
+    return s;
+  }
+  void clear() { kf_.clear(); alive_.clear(); map_.clear(); }
+  // flags [size] of a container of KF* (GetConnectedKeyFrames)
+  template <class Set> std::vector<uint8_t> flags(const Set& connected) const {
+    std::vector<uint8_t> f((size_t)next(), 0);
+    for (const KF* p : connected) {
+      const int32_t s = slot(p);
+      if (s >= 0) f[s] = 1;
+    }
+    return f;
+  }
+  // [size][MCS_KFDB_NEIGH] slots of neighbours(kf) = GetBestCovisibilityKeyFrames(10), -1 padded;
+  // a neighbour that was never added is -1 too and keeps its position
+  template <class Fn> std::vector<int32_t> neighbours(Fn&& best_covisibles) const {
+    std::vector<int32_t> ng((size_t)next() * MCS_KFDB_NEIGH, -1);
+    for (int32_t s = 0; s < next(); s++) {
+      int k = 0;
+      for (const KF* p : best_covisibles(kf_[s])) {
+        if (k == MCS_KFDB_NEIGH) break;
+        ng[(size_t)s * MCS_KFDB_NEIGH + k++] = slot(p);
+      }
+    }
+    return ng;
+  }
+
+ private:
+  std::vector<const KF*> kf_;
+  std::vector<uint8_t> alive_;
+  std::unordered_map<const KF*, int32_t> map_;
+};
+
+// KF is the caller's keyframe type and F its frame type.  Needed from them, as in the reference:
+//   mnId, mBowVec (an ordered container of (word, value) pairs: DBoW2::BowVector),
+//   GetConnectedKeyFrames() and GetBestCovisibilityKeyFrames(int) -> containers of KF*, isBad().
+template <class KF>
+class KeyFrameDatabase {
+ public:
+  KeyFrameDatabase(const mcs_vocab* voc, int max_keyframes, int max_entries, int device = 0) {
+    check(mcs_kfdb_create(device, voc, max_keyframes, max_entries, &db_), "mcs_kfdb_create");
+  }
+  ~KeyFrameDatabase() { mcs_kfdb_destroy(db_); }
+  KeyFrameDatabase(const KeyFrameDatabase&) = delete;
+  KeyFrameDatabase& operator=(const KeyFrameDatabase&) = delete;
+
+  void add(KF* pKF) {
+    std::vector<uint32_t> w;
+    std::vector<double> v;
+    unpack(pKF->mBowVec, w, v);
+    int32_t slot = -1;
+    // mRelocScore is uninitialised in the reference; 0 is this adapter's choice (mcs_kfdb.h)
+    check(mcs_kfdb_add(db_, w.data(), v.data(), (int32_t)w.size(), 0.0, &slot), "mcs_kfdb_add");
+    slots_.bind(pKF, slot);
+  }
+  void erase(KF* pKF) {
+    const int32_t s = slots_.erase(pKF);
+    if (s >= 0) check(mcs_kfdb_erase(db_, s, nullptr), "mcs_kfdb_erase");
+  }
+  void clear() {
+    check(mcs_kfdb_clear(db_, nullptr), "mcs_kfdb_clear");
+    slots_.clear();
+  }
+
+  // the minScore loop of cLoopClosing::DetectLoop (src/cLoopClosing.cpp:141-157)
+  double MinScore(KF* pKF) {
+    std::vector<uint32_t> w;
+    std::vector<double> v;
+    unpack(pKF->mBowVec, w, v);
+    std::vector<int32_t> list;
+    for (KF* p : pKF->GetConnectedKeyFrames())
+      if (!p->isBad()) list.push_back(slots_.slot(p));
+    double m = 1.0;
+    check(mcs_kfdb_min_score(db_, w.data(), v.data(), (int32_t)w.size(), list.data(), (int32_t)list.size(), &m),
+          "mcs_kfdb_min_score");
+    return m;
+  }
+
+  std::vector<KF*> DetectLoopCandidates(KF* pKF, double minScore) {
+    std::vector<uint32_t> w;
+    std::vector<double> v;
+    unpack(pKF->mBowVec, w, v);
+    const std::vector<uint8_t> conn = slots_.flags(pKF->GetConnectedKeyFrames());
+    const std::vector<int32_t> ng = neighbours();
+    std::vector<int32_t> cand((size_t)slots_.next() + 1);
+    int32_t n = 0;
+    check(mcs_kfdb_detect_loop(db_, w.data(), v.data(), (int32_t)w.size(), (int64_t)pKF->mnId, conn.data(), minScore,
+                               ng.data(), cand.data(), slots_.next(), &n, nullptr, nullptr), "mcs_kfdb_detect_loop");
+    return pointers(cand, n);
+  }
+
+  template <class F>
+  std::vector<KF*> DetectRelocalisationCandidates(F* frame) {
+    std::vector<uint32_t> w;
+    std::vector<double> v;
+    unpack(frame->mBowVec, w, v);
+    const std::vector<int32_t> ng = neighbours();
+    std::vector<int32_t> cand((size_t)slots_.next() + 1);
+    int32_t n = 0;
+    check(mcs_kfdb_detect_reloc(db_, w.data(), v.data(), (int32_t)w.size(), (int64_t)frame->mnId, ng.data(),
+                                cand.data(), slots_.next(), &n, nullptr, nullptr), "mcs_kfdb_detect_reloc");
+    return pointers(cand, n);
+  }
+
+  const KfSlots<KF>& slots() const { return slots_; }
+
+ private:
+  template <class Bow> static void unpack(const Bow& bow, std::vector<uint32_t>& w, std::vector<double>& v) {
+    for (const auto& e : bow) { w.push_back((uint32_t)e.first); v.push_back((double)e.second); }
+  }
+  std::vector<int32_t> neighbours() const {
+    return slots_.neighbours([](const KF* k) { return const_cast<KF*>(k)->GetBestCovisibilityKeyFrames(MCS_KFDB_NEIGH); });
+  }
+  std::vector<KF*> pointers(const std::vector<int32_t>& cand, int32_t n) const {
+    std::vector<KF*> out;
+    for (int32_t i = 0; i < n; i++) out.push_back(const_cast<KF*>(slots_.kf(cand[i])));
+    return out;
+  }
+  mcs_kfdb* db_ = nullptr;
+  KfSlots<KF> slots_;
+};
 
 }  // namespace mcs

@@ -197,6 +197,23 @@ SIGNATURES = {
     "mcs_vocab_info": (_I32, [_P, _P]),
     "mcs_vocab_transform_words_device": (_I32, [_P, _P, _I32, _I32, _P, _P, _P, _P]),
     "mcs_vocab_transform": (_I32, [_P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "mcs_bow_vector_device": (_I32, [_P, _P, _P, _P, _I32, _P, _P, _P, _P]),
+    # keyframe database (include/mcs_kfdb.h; wrappers in mcs_amd/kfdb.py)
+    "mcs_kfdb_create_n": (_I32, [_I32, _I32, _I32, _I32, _I32, _P]),
+    "mcs_kfdb_create": (_I32, [_I32, _P, _I32, _I32, _P]),
+    "mcs_kfdb_destroy": (None, [_P]),
+    "mcs_kfdb_size": (_I32, [_P]),
+    "mcs_kfdb_add_device": (_I32, [_P, _P, _P, _P, _I32, ctypes.c_double, _P, _P]),
+    "mcs_kfdb_erase": (_I32, [_P, _I32, _P]),
+    "mcs_kfdb_clear": (_I32, [_P, _P]),
+    "mcs_kfdb_min_score_device": (_I32, [_P, _P, _P, _I32, _P, _P]),
+    "mcs_kfdb_detect_loop_device": (_I32, [_P, _P, _I64, _P, _P, _P, _P, _P]),
+    "mcs_kfdb_detect_reloc_device": (_I32, [_P, _P, _I64, _P, _P, _P]),
+    "mcs_kfdb_members_device": (_I32, [_P] * 8),
+    "mcs_kfdb_add": (_I32, [_P, _P, _P, _I32, ctypes.c_double, _P]),
+    "mcs_kfdb_min_score": (_I32, [_P, _P, _P, _I32, _P, _I32, _P]),
+    "mcs_kfdb_detect_loop": (_I32, [_P, _P, _P, _I32, _I64, _P, ctypes.c_double, _P, _P, _I32, _P, _P, _P]),
+    "mcs_kfdb_detect_reloc": (_I32, [_P, _P, _P, _I32, _I64, _P, _P, _I32, _P, _P, _P]),
     # omni camera mirror masks (include/mcs_cammodel.h)
     "mcs_mirror_mask_layout": (_I32, [_I32, _I32, _I32, _P, _P, _P, _P]),
     "mcs_create_mirror_mask_device": (_I32, [ctypes.c_double, ctypes.c_double, _I32, _I32, _I32, _P, _P]),

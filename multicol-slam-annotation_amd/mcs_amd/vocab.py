@@ -135,6 +135,26 @@ class Vocabulary:
                                     weight.data_ptr(), node.data_ptr(), stream)
         return word, weight, node
 
+    def bow_vector_device(self, ws, d_word, d_weight, n, d_bow_word, d_bow_value, d_bow_n, stream=None):
+        """mcs_bow_vector_device on raw device pointers: the BowVector of the per-descriptor
+        d_word / d_weight [n] of transform_words_device, count left on the device.  ws is a
+        mcs_amd.bow_match.Workspace (n <= its max_kp)."""
+        _check(_lib().mcs_bow_vector_device(ws._h if ws is not None else None, self._h, d_word, d_weight, int(n),
+                                            d_bow_word, d_bow_value, d_bow_n, stream))
+
+    def bow_vector(self, ws, word, weight):
+        """torch word (int32) / weight (float64) [n] on cuda -> (bow_word int32 [n], bow_value
+        float64 [n], bow_n int32 [1]) torch tensors; the first bow_n entries count."""
+        import torch
+        n = word.shape[0]
+        bw = torch.zeros(max(n, 1), dtype=torch.int32, device=word.device)
+        bv = torch.zeros(max(n, 1), dtype=torch.float64, device=word.device)
+        bn = torch.zeros(1, dtype=torch.int32, device=word.device)
+        stream = torch.cuda.current_stream(word.device).cuda_stream
+        self.bow_vector_device(ws, word.data_ptr(), weight.data_ptr(), n, bw.data_ptr(), bv.data_ptr(),
+                               bn.data_ptr(), stream)
+        return bw, bv, bn
+
     def transform(self, desc, levelsup=4):
         """Host uint8 [n, 32] -> (BowVector dict word->value, FeatureVector dict node->[i])."""
         desc = np.ascontiguousarray(desc, dtype=np.uint8).reshape(-1, 32)
