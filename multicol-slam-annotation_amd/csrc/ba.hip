@@ -14,17 +14,17 @@
 //
 // Every reduction runs in a fixed order (no float atomics): results are bitwise
 // reproducible run to run.  The LM accept/reject decision needs two scalars per trial
-// (robust chi2, model decrease), read back by the host driver.
+// (robust chi2, model decrease); lm_control.hpp decides, on the device or driven from the host.
 #include "host_util.hpp"
 #include "../../include/mcs_ba.h"
 #include "ldlt.hpp"
 #include "ba_structure.hpp"
+#include "lm_control.hpp"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <limits>
 #include <memory>
 #include <new>
 #include <thread>
@@ -217,24 +217,6 @@ __device__ __forceinline__ void huber(double e, double delta, double dsqr, doubl
 // ---------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------
-// Device-side Levenberg-Marquardt control (Optimizer::run_device): the accept / reject
-// decision, the lambda schedule, Raul's nBad stop and the terminate action of g2o run in
-// k_edges_end after every trial, so the host enqueues trial after trial without reading anything
-// back.  Kernels of a step that is no longer needed (done) return at once; the linearisation
-// of a step runs only when the previous trial ended an iteration (lin).
-constexpr int kLmTraceCap = 64;
-struct LmCtl {
-  double lambda, currentChi, iniChi, lastChi, tau, gain_threshold;
-  double chi0, lambda_final;
-  int ni, qmax, nBad, it, iter;
-  int done, lin, restore, stop_out, ext_stop;
-  int dev_err;       // a solve's hand-off wait timed out (ldlt::kFlagTimeout): the run is aborted
-  int spec_lin;      // k_edges_end linearises every trial into the other Jacobian buffer
-  int jbuf;          // the linearisation buffer of the current iteration (0 / 1)
-  int max_iterations, max_trials, terminate_max_iter;
-  unsigned arrive;   // k_edges_end's arrival counter (0 between launches)
-  double trace[kLmTraceCap];
-};
 // host-coherent progress word of run_device (written by k_edges_end after every step)
 struct LmSig { uint64_t seq; int32_t done, iter; int32_t ext_stop, pad_; };
 
@@ -448,26 +430,17 @@ __global__ __launch_bounds__(1024) void k_reduce3(Sum3 q, const int* flag, Trial
   }
 }
 
-// ---- device-driven Levenberg-Marquardt control (one thread) ------------------------------
-// x^3 rounded once (double-double product), the value std::pow(x, 3) returns: host and device
-// (and every rank) take the identical lambda step
-__host__ __device__ inline double cube_rn(double x) {
-  const double p = x * x;
-  const double pe = __builtin_fma(x, x, -p);       // x^2 = p + pe exactly
-  const double h = p * x;
-  // overflow: pow(x, 3) returns +-inf (the error terms would turn it into NaN, and the LM's
-  // alpha = 1 - pow(2 rho - 1, 3) must become -inf so that lambda *= 1/3; g2o_solver.npz
-  // scenario 27 has such a step)
-  if (!__builtin_isfinite(h)) return h;
-  const double he = __builtin_fma(p, x, -h);       // p x = h + he exactly
-  return h + (he + pe * x);
+// after a trial (k_edges_end's last workgroup, one thread): lm_step (lm_control.hpp) with the
+// caller's stop flag as the host last published it; flag = the solve's status bits
+__device__ void lm_control(LmCtl* c, const double* sc, int flag, LmSig* sig) {
+  const int stop = __hip_atomic_load(&sig->ext_stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0;
+  lm_step(c, sc, (flag & ldlt::kFlagZeroPivot) != 0, (flag & ldlt::kFlagTimeout) != 0, stop);
 }
 
 // The end of a device-driven step, run by the last-arriving workgroup of k_edges_end: the
 // trial's three sums from the workgroup partials (each summed exactly as k_reduce3's 1024-thread
 // workgroups do: 1024 strided slots, then the LDS tree -- emulated here by kRedNT threads, so
 // the bits are the same), the LM control (lm_control) and the pop of a rejected trial.
-__device__ void lm_control(LmCtl* c, const double* sc, int flag, LmSig* sig);
 struct LmEnd { double* sc; const int* flag; LmSig* sig; uint64_t seq; LmCtl* host_ctl; };
 #ifndef MCS_LM_AHEAD
 #define MCS_LM_AHEAD 2      // LM steps the host keeps enqueued ahead of the device
@@ -639,22 +612,10 @@ __global__ __launch_bounds__(kEdgeEndNT) void k_edges_end(Dev d0, Sum3 q, LmEnd 
   lm_end_body(d0, q, le);
 }
 
-// chi2 of the starting point -> currentChi (the optimize() call's activeRobustChi2)
-__device__ __forceinline__ void lm_start_body(LmCtl* c, double chi) {
-  c->chi0 = chi;
-  c->currentChi = chi;
-  c->iniChi = chi;
-}
+// chi2 of the starting point -> currentChi (lm_control.hpp)
 __global__ void k_lm_start(LmCtl* c, const double* sc) {
   if (threadIdx.x != 0) return;
   lm_start_body(c, sc[0]);
-}
-// lambda of iteration 0: tau * max diagonal (computeLambdaInit,
-// optimization_algorithm_levenberg.cpp:166-180); pt / pose = max |diagonal| of Hll / Hpp
-__device__ __forceinline__ void lm_lambda0_body(LmCtl* c, double pt, double pose) {
-  c->lambda = c->tau * fmax(pt, pose);
-  c->ni = 2;
-  c->nBad = 0;
 }
 // the LM control block of a run, by value (no pageable host copy on the stream)
 // (+ the per-block chunk counters of k_schur's fused fin, zeroed)
@@ -670,79 +631,6 @@ __global__ void k_ctl_init(LmCtl h0, LmCtl* c, uint32_t* blk_arrive, int nblk) {
 __global__ void k_lm_lambda0(LmCtl* c, const double* sc) {
   if (threadIdx.x != 0 || c->done) return;
   lm_lambda0_body(c, sc[1], sc[2]);
-}
-// after a trial (k_edges_end's last workgroup, one thread): OptimizationAlgorithmLevenberg::solve's accept / reject
-// (optimization_algorithm_levenberg.cpp:99-163) and, when the iteration ends, the terminate
-// action (sparse_optimizer_terminate_action.cpp:43-72) -- the arithmetic of the host driver
-// statement for statement.  sc = {robust chi2, points' model decrease, poses' model
-// decrease}; flag = the solve failed (zero pivot).
-__device__ void lm_control(LmCtl* c, const double* sc, int flag, LmSig* sig) {
-  {
-    const int stop = __hip_atomic_load(&sig->ext_stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0;
-    c->ext_stop = stop;
-    if (flag & ldlt::kFlagTimeout) {   // x is garbage: no LM decision, the host reports MCS_ERR_HIP
-      c->dev_err = 1;
-      c->done = 1;
-      c->restore = 1;                  // k_edges_end pops the trial's state
-      return;
-    }
-    double tempChi = sc[0];
-    if (flag & ldlt::kFlagZeroPivot) tempChi = 1.7976931348623157e308;
-    double rho = c->currentChi - tempChi;
-    double scale = sc[2] + sc[1];
-    scale += 1e-3;
-    rho /= scale;
-    if (rho > 0 && isfinite(tempChi)) {
-      double alpha = 1. - cube_rn(2 * rho - 1);
-      alpha = fmin(alpha, 2. / 3.);
-      c->lambda *= fmax(1. / 3., alpha);
-      c->ni = 2;
-      c->currentChi = tempChi;
-      c->restore = 0;
-      if (c->spec_lin) c->jbuf ^= 1;   // the trial's linearisation (k_edges_end) is current
-    } else {
-      c->lambda *= c->ni;
-      c->ni *= 2;
-      c->restore = 1;   // k_edges_end pops the state right after this decision
-    }
-    c->qmax++;
-    if (rho < 0 && c->qmax < c->max_trials && !stop) {
-      c->lin = 0;       // the next step retries the trial with the larger lambda
-    } else {
-      int result = 0;
-      if (c->qmax == c->max_trials || rho == 0) result = 1;
-      else {
-        if ((c->iniChi - c->currentChi) * 1e3 < c->iniChi) c->nBad++;
-        else c->nBad = 0;
-        if (c->nBad >= 3) result = 1;
-      }
-      c->it++;
-      const int i = c->iter;
-      const double cur = c->currentChi;
-      if (i < kLmTraceCap) c->trace[i] = cur;
-      int stopOpt = 0;
-      if (i == 0) c->lastChi = cur;
-      else {
-        if (i < c->terminate_max_iter) {
-          const double gain = (c->lastChi - cur) / cur;
-          c->lastChi = cur;
-          if (gain >= 0 && gain < c->gain_threshold) stopOpt = 1;
-        } else {
-          stopOpt = 1;
-        }
-      }
-      if (stopOpt) c->stop_out = 1;
-      c->lambda_final = c->lambda;
-      c->iter = i + 1;
-      if (c->iter >= c->max_iterations || stop || stopOpt || result != 0) {
-        c->done = 1;
-      } else {
-        c->lin = 1;
-        c->qmax = 0;
-        c->iniChi = c->currentChi;
-      }
-    }
-  }
 }
 
 // Test hooks (mcs_ba_lm_replay, mcs_ba_huber_eval): the production device functions replayed on
@@ -762,7 +650,7 @@ __global__ void k_lm_replay(LmCtl* c, LmSig* sig, const double* in, const double
     const double* tr = trials + 4 * t;
     const double sc[3] = {tr[0], tr[1], tr[2]};
     const double lam = c->lambda;
-    lm_control(c, sc, tr[3] != 0.0 ? 1 : 0, sig);
+    lm_control(c, sc, tr[3] != 0.0 ? ldlt::kFlagZeroPivot : 0, sig);
     double* o = out + 10 * t;
     o[0] = lam; o[1] = c->lambda; o[2] = c->ni; o[3] = c->restore ? 0.0 : 1.0; o[4] = c->qmax;
     o[5] = c->nBad; o[6] = c->iter; o[7] = c->done; o[8] = c->stop_out; o[9] = c->currentChi;
@@ -1816,7 +1704,6 @@ struct Optimizer {
   int* d_flag = nullptr;
   ldlt::Work lw;
   unsigned g_state = 1;
-  bool sig_path = false;
   hipError_t he = hipSuccess;
   // LocalBA culling on the device (mcs_local_ba_ex with the device-driven LM): set lba and
   // lba_extra before setup(); lba_tail picks what run_device does after the LM loop
@@ -2086,7 +1973,6 @@ struct Optimizer {
     d.n_pose_dbl = 6 * p->n_poses; d.n_point_dbl = 3 * p->n_points;
     d.flag = d_flag;
     g_state = gb(std::max(d.n_pose_dbl, d.n_point_dbl));
-    sig_path = !sharded && d.nae <= 32768 && s.nl <= 32768 && s.np <= 32768;
     const int rp = enqueue_pairs();
     hc.mark(c->host_ms, 2);
     return rp;
@@ -2202,7 +2088,6 @@ struct Optimizer {
     s.aedge.swap(keep);
     nae_glob = d.nae;
     nl_glob = nl_left;
-    sig_path = !sharded && d.nae <= 32768 && s.nl <= 32768 && s.np <= 32768;
     hc.mark(c->host_ms, 4);
     return MCS_OK;
   }
@@ -2213,7 +2098,6 @@ struct Optimizer {
     d.elevel = L.level;   // round 1's list; its level-1 edges are skipped (terms zeroed)
     nae_glob = lba_res[0];
     nl_glob = lba_res[2];
-    sig_path = !sharded && d.nae <= 32768 && s.nl <= 32768 && s.np <= 32768;
   }
 
   // run_device's tail for LocalBA (lba_tail 1..3): chi2 of every edge at the final estimate,
@@ -2287,6 +2171,24 @@ struct Optimizer {
     return MCS_OK;
   }
 
+  // the host-driven loop learns a trial's outcome from k_reduce3's released sequence numbers
+  // (one launch for the three sums) instead of a readback copy and a stream synchronisation
+  bool sig_path() const { return !sharded && d.nae <= 32768 && s.nl <= 32768 && s.np <= 32768; }
+
+  // the report of a finished run from its control block (run: its own; run_device: the copy
+  // k_edges_end left in pinned memory); stop = the stop flag afterwards
+  void write_report(mcs_ba_report* rep, const LmCtl& k, int32_t stop) const {
+    if (!rep) return;
+    rep->n_active_edges = nae_glob;
+    rep->n_active_poses = s.np;
+    rep->n_active_points = nl_glob;
+    rep->chi2_initial = k.chi0;
+    rep->chi2_final = k.currentChi;
+    rep->iterations = k.it;
+    rep->lambda_final = k.lambda_final;
+    rep->stop_flag = stop;
+  }
+
   // the LM loop runs on the device (run_device) for these options
   bool device_driven(const mcs_ba_options* o, const mcs_ba_report* rep) const {
     const bool long_trace = rep && rep->trace_chi2 && rep->trace_cap > kLmTraceCap &&
@@ -2306,12 +2208,6 @@ struct Optimizer {
     auto rec = [&](int k) { if (c->timing) (void)hipEventRecord(c->ev[k], st); };
     auto ms = [&](int a, int b) { float f = 0.f; (void)hipEventElapsedTime(&f, c->ev[a], c->ev[b]); return (double)f; };
     int rc;
-    if (rep) {
-      rep->n_active_edges = nae_glob;
-      rep->n_active_poses = s.np;
-      rep->n_active_points = nl_glob;
-      rep->iterations = 0;
-    }
     // control state agreed by all ranks: the caller's stop flag is folded into every scalar
     // exchange, so no rank leaves the LM loop alone
     volatile int32_t aux = 0;
@@ -2353,7 +2249,7 @@ struct Optimizer {
       rec(5);
       hipLaunchKernelGGL(k_update, dim3(gb(4 * s.nl + s.np)), dim3(256), 0, st, d);
       hipLaunchKernelGGL(k_edges, dim3(gb(d.nae)), dim3(256), 0, st, d, 0);
-      if (sig_path) {
+      if (sig_path()) {
         Sum3 q{{d.rchi, d.red, d.red + s.nl}, {d.nae, s.nl, s.np}};
         hipLaunchKernelGGL(k_reduce3, dim3(3), dim3(1024), 0, st, q, (const int*)d_flag, c->sig, ++c->sig_seq);
       } else if (sharded) {
@@ -2383,7 +2279,7 @@ struct Optimizer {
     // the stream now and then so a failed launch cannot spin forever; else synchronise the
     // stream after the readback copy.  Fills pinned[0..2] and the solve flag.
     auto wait_trial = [&](int* fl) -> int {
-      if (!sig_path) {
+      if (!sig_path()) {
         MCS_HIP_CHECK(hipStreamSynchronize(st));
         std::memcpy(fl, c->pinned + 5, sizeof(*fl));
         return MCS_OK;
@@ -2412,17 +2308,21 @@ struct Optimizer {
       if (c->timing) MCS_HIP_CHECK(hipStreamSynchronize(st));   // events complete
       return MCS_OK;
     };
-    double chi0 = 0;
+    // the same controller as the device-driven loop (lm_control.hpp), driven from the host:
+    // every rank feeds it the same agreed sums, solve flag and stop flag
+    LmCtl ctl;
+    lm_init(ctl, *o);
     if ((s.np + nl_glob) == 0 || nae_glob == 0) {
-      if (rep) rep->chi2_initial = rep->chi2_final = 0;
+      ctl.done = 1;
     } else {
+      double chi0 = 0;
       if ((rc = chi_now(&chi0))) return rc;
-      if (rep) rep->chi2_initial = chi0;
-      double lambda = 0, lastChi = 0;
-      int ni = 2, nBad = 0, it = 0;
-      bool ok = true;
-      double currentChi = chi0;
-      for (int i = 0; i < o->max_iterations && !agreed_stop && ok; i++) {
+      lm_start_body(&ctl, chi0);
+      ctl.done = (o->max_iterations <= 0 || agreed_stop) ? 1 : 0;
+    }
+    bool lin_pending = false;
+    while (!ctl.done) {
+      if (ctl.lin) {
         // ---- OptimizationAlgorithmLevenberg::solve(i)
         // The robust chi2 of the linearisation point equals the chi2 the previous iteration
         // ended with (same kernel, same state: accepted trial or restored backup), so only
@@ -2432,95 +2332,49 @@ struct Optimizer {
         hipLaunchKernelGGL(k_build, dim3((unsigned)s.np + (unsigned)((4 * s.nl + kBuildNT - 1) / kBuildNT)), dim3(kBuildNT), 0, st, d);
         rec(1);
         c->n_iter++;
-        bool lin_pending = c->timing;
+        lin_pending = c->timing;
         if ((rc = allreduce(MCS_REDUCE_SUM, X.hdiag, 12 * (size_t)s.np))) return rc;   // hdiag | bpf
-        if (i == 0) {
+        if (ctl.iter == 0) {
           reduce_dev<true>(d.red, s.nl, d_scalar + 1, d_part, st);
           reduce_dev<true>(d.hdiag, 6 * s.np, d_scalar + 2, d_part, st);
           MCS_HIP_CHECK(hipMemcpyAsync(c->pinned + 1, d_scalar + 1, 16, hipMemcpyDeviceToHost, st));
           MCS_HIP_CHECK(hipStreamSynchronize(st));
           double mx = std::max(c->pinned[1], c->pinned[2]);
           if ((rc = allreduce_host(&mx, 1, MCS_REDUCE_MAX, sc))) return rc;
-          lambda = o->tau * mx; ni = 2; nBad = 0;
+          lm_lambda0_body(&ctl, mx, mx);
         }
-        const double iniChi = currentChi;
-        double rho = 0;
-        int qmax = 0;
-        do {
-          // lambda reaches the kernels by value (Dev d), no upload; a captured graph of the trial
-          // (replayed per trial) measured no faster than these direct launches
-          d.lam = lambda;
-          d.lam0 = sh.rank == 0 ? lambda : 0.0;
-          if ((rc = enqueue_trial(*stop != 0))) return rc;
-          int fl;   // identical on every rank (same reduced system)
-          if ((rc = wait_trial(&fl))) return rc;
-          if (fl & ldlt::kFlagTimeout) {
-            set_error("BA: the LDL^T solve's hand-off wait timed out (ldlt kFlagTimeout); result discarded");
-            return MCS_ERR_HIP;
-          }
-          if (c->timing) {
-            if (lin_pending) { c->acc_ms[0] += ms(0, 1); lin_pending = false; }
-            if (sh.ordered) c->acc_ms[2] += ms(3, 4);
-            c->acc_ms[1] += ms(2, 3);
-            c->acc_ms[3] += ms(4, 5);
-            c->acc_ms[4] += ms(5, 6);
-            c->n_trial++;
-            c->last_n = n;
-          }
-          // sharded: summed on the device by enqueue_trial
-          const double tr[3] = {c->pinned[0], c->pinned[1], sharded ? c->pinned[2] : 0.0};
-          const double scale_pose = sharded ? c->pinned[3] : c->pinned[2];
-          agreed_stop = sharded ? tr[2] > 0 : *stop != 0;
-          double tempChi = tr[0];
-          if (fl & ldlt::kFlagZeroPivot) tempChi = std::numeric_limits<double>::max();
-          rho = currentChi - tempChi;
-          double scale = scale_pose + tr[1];
-          scale += 1e-3;
-          rho /= scale;
-          if (rho > 0 && std::isfinite(tempChi)) {
-            double alpha = 1. - cube_rn(2 * rho - 1);
-            alpha = std::min(alpha, 2. / 3.);
-            lambda *= std::max(1. / 3., alpha);
-            ni = 2;
-            currentChi = tempChi;
-          } else {
-            lambda *= ni;
-            ni *= 2;
-            hipLaunchKernelGGL(k_restore, dim3(g_state), dim3(256), 0, st, d);  // pop
-          }
-          qmax++;
-        } while (rho < 0 && qmax < o->max_trials && !agreed_stop);
-        int result = 0;
-        if (qmax == o->max_trials || rho == 0) result = 1;
-        else {
-          if ((iniChi - currentChi) * 1e3 < iniChi) nBad++;
-          else nBad = 0;
-          if (nBad >= 3) result = 1;
-        }
-        ok = (result == 0);
-        ++it;
-        // ---- SparseOptimizerTerminateAction (post-iteration): activeRobustChi2 of the
-        // current state == currentChi (see above); identical on every rank
-        const double cur = currentChi;
-        if (rep && rep->trace_chi2 && i < rep->trace_cap) rep->trace_chi2[i] = cur;
-        if (i == 0) lastChi = cur;
-        else {
-          bool stopOpt = false;
-          if (i < o->terminate_max_iter) {
-            const double gain = (lastChi - cur) / cur;
-            lastChi = cur;
-            if (gain >= 0 && gain < o->gain_threshold) stopOpt = true;
-          } else {
-            stopOpt = true;
-          }
-          if (stopOpt) { *stop = 1; agreed_stop = 1; }
-        }
-        if (rep) rep->lambda_final = lambda;
       }
-      if (rep) rep->iterations = it;
-      if (rep) rep->chi2_final = currentChi;
+      // lambda reaches the kernels by value (Dev d), no upload; a captured graph of the trial
+      // (replayed per trial) measured no faster than these direct launches
+      d.lam = ctl.lambda;
+      d.lam0 = sh.rank == 0 ? ctl.lambda : 0.0;
+      if ((rc = enqueue_trial(*stop != 0))) return rc;
+      int fl;   // identical on every rank (same reduced system)
+      if ((rc = wait_trial(&fl))) return rc;
+      // sharded: chi2, the points' decrease and the stop flag summed on the device by enqueue_trial
+      const double tr[3] = {c->pinned[0], c->pinned[1], sharded ? c->pinned[3] : c->pinned[2]};
+      agreed_stop = sharded ? c->pinned[2] > 0 : *stop != 0;
+      const int i = ctl.iter;
+      lm_step(&ctl, tr, (fl & ldlt::kFlagZeroPivot) != 0, (fl & ldlt::kFlagTimeout) != 0, agreed_stop);
+      if (ctl.dev_err) {
+        set_error("BA: the LDL^T solve's hand-off wait timed out (ldlt kFlagTimeout); result discarded");
+        return MCS_ERR_HIP;
+      }
+      if (c->timing) {
+        if (lin_pending) { c->acc_ms[0] += ms(0, 1); lin_pending = false; }
+        if (sh.ordered) c->acc_ms[2] += ms(3, 4);
+        c->acc_ms[1] += ms(2, 3);
+        c->acc_ms[3] += ms(4, 5);
+        c->acc_ms[4] += ms(5, 6);
+        c->n_trial++;
+        c->last_n = n;
+      }
+      if (ctl.restore) hipLaunchKernelGGL(k_restore, dim3(g_state), dim3(256), 0, st, d);  // pop
+      // an iteration ended: this path's trace is not bounded by kLmTraceCap
+      if (ctl.iter != i && rep && rep->trace_chi2 && i < rep->trace_cap) rep->trace_chi2[i] = ctl.currentChi;
+      if (ctl.stop_out) *stop = 1;   // the terminate action raised the flag
     }
-    if (rep) rep->stop_flag = *stop;
+    write_report(rep, ctl, *stop);
     return download(poses, points, edge_chi2);
   }
 
@@ -2564,24 +2418,13 @@ struct Optimizer {
   // are k_edges_end's.  Kernels of steps past the end return at once.
   int run_device(const mcs_ba_options* o, double* poses, double* points, double* edge_chi2,
                  volatile int32_t* stop_flag, mcs_ba_report* rep) {
-    if (rep) {
-      rep->n_active_edges = nae_glob;
-      rep->n_active_poses = s.np;
-      rep->n_active_points = nl_glob;
-      rep->iterations = 0;
-    }
     volatile int32_t aux = 0;
     volatile int32_t* stop = stop_flag ? stop_flag : &aux;
     LmCtl* dctl = (LmCtl*)c->alloc(sizeof(LmCtl));
     if (!dctl) { set_error("BA: out of device memory"); return MCS_ERR_HIP; }
     LmCtl h0;
-    std::memset(&h0, 0, sizeof(h0));
-    h0.tau = o->tau; h0.gain_threshold = o->gain_threshold;
-    h0.max_iterations = o->max_iterations; h0.max_trials = o->max_trials;
-    h0.terminate_max_iter = o->terminate_max_iter;
-    h0.lin = 1; h0.ni = 2;
+    lm_init(h0, *o);
     h0.spec_lin = d.alt_err ? 1 : 0;   // k_edges_end linearises every trial (see k_edges_end)
-    h0.jbuf = 0;
     const bool empty = (s.np + nl_glob) == 0 || nae_glob == 0;
     h0.done = (empty || o->max_iterations <= 0 || *stop != 0) ? 1 : 0;
     c->lsig->ext_stop = *stop != 0;
@@ -2691,16 +2534,10 @@ struct Optimizer {
       return MCS_ERR_HIP;
     }
     if (hc->stop_out) *stop = 1;   // the terminate action raised the flag (host-visible)
-    if (rep) {
-      rep->chi2_initial = empty ? 0.0 : hc->chi0;
-      rep->chi2_final = empty ? 0.0 : hc->currentChi;
-      rep->iterations = hc->it;
-      rep->lambda_final = hc->lambda_final;
-      if (rep->trace_chi2)
-        for (int i = 0; i < std::min(hc->iter, std::min(rep->trace_cap, kLmTraceCap)); i++)
-          rep->trace_chi2[i] = hc->trace[i];
-      rep->stop_flag = *stop;
-    }
+    write_report(rep, *hc, *stop);   // (an empty graph never ran k_lm_start: chi0 = currentChi = 0)
+    if (rep && rep->trace_chi2)
+      for (int i = 0; i < std::min(hc->iter, std::min(rep->trace_cap, kLmTraceCap)); i++)
+        rep->trace_chi2[i] = hc->trace[i];
     return MCS_OK;
   }
 };
@@ -2908,6 +2745,18 @@ int mcs_local_ba_ex(mcs_ba_ctx* c, const mcs_ba_problem* p, const int32_t* point
       if (--obs_left[pt] < 2) pt_bad[pt] = 1;
     }
   };
+  // the host-culled rounds' end (:885-902): the points to write back are those not bad, with
+  // TotalNrObservations() > 1 and >= 2 vertex edges
+  auto write_out = [&]() {
+    *write_back = 1;
+    if (point_write) {
+      std::vector<int32_t> edges_all(p->n_points, 0);
+      for (int e = 0; e < p->n_edges; e++) edges_all[p->edge_point[e]]++;
+      for (int i = 0; i < p->n_points; i++)
+        point_write[i] = !pt_bad[i] && edges_left[i] > 1 && edges_all[i] >= 2;
+    }
+    return MCS_OK;
+  };
   o.max_iterations = 10;
   // round 1 builds the structure and uploads the problem; round 2 (the same graph with the
   // culled edges at level 1) reuses both (Optimizer::remask) unless a pose left the system
@@ -2950,14 +2799,7 @@ int mcs_local_ba_ex(mcs_ba_ctx* c, const mcs_ba_problem* p, const int32_t* point
       *write_back = 1;
       return MCS_OK;
     }
-    *write_back = 1;
-    if (point_write) {
-      std::vector<int32_t> edges_all(p->n_points, 0);
-      for (int e = 0; e < p->n_edges; e++) edges_all[p->edge_point[e]]++;
-      for (int i = 0; i < p->n_points; i++)
-        point_write[i] = !pt_bad[i] && edges_left[i] > 1 && edges_all[i] >= 2;
-    }
-    return MCS_OK;
+    return write_out();
   }
   int rc = opt.setup(poses, points, level.data(), nullptr);
   if (rc) return rc;
@@ -2979,14 +2821,7 @@ int mcs_local_ba_ex(mcs_ba_ctx* c, const mcs_ba_problem* p, const int32_t* point
   if (rc) return rc;
   if (r2->n_active_poses + r2->n_active_points == 0) return MCS_OK;   // :822-826
   cull(false);
-  *write_back = 1;
-  if (point_write) {   // :885-902: not bad, TotalNrObservations() > 1, >= 2 vertex edges
-    std::vector<int32_t> edges_all(p->n_points, 0);
-    for (int e = 0; e < p->n_edges; e++) edges_all[p->edge_point[e]]++;
-    for (int i = 0; i < p->n_points; i++)
-      point_write[i] = !pt_bad[i] && edges_left[i] > 1 && edges_all[i] >= 2;
-  }
-  return MCS_OK;
+  return write_out();
 }
 
 int mcs_local_ba(mcs_ba_ctx* c, const mcs_ba_problem* p, double* poses, double* points,
@@ -3079,11 +2914,7 @@ int mcs_ba_lm_replay(int32_t device, const mcs_ba_options* o, const double* in3,
   }
   if (int rc = host::open_device(device, "lm_replay")) return rc;
   LmCtl h0;
-  std::memset(&h0, 0, sizeof(h0));
-  h0.tau = o->tau; h0.gain_threshold = o->gain_threshold;      // as run_device sets them
-  h0.max_iterations = o->max_iterations; h0.max_trials = o->max_trials;
-  h0.terminate_max_iter = o->terminate_max_iter;
-  h0.lin = 1; h0.ni = 2;
+  lm_init(h0, *o);
   h0.done = o->max_iterations <= 0 ? 1 : 0;
   host::DevBufs B;
   LmCtl* dc = B.up(&h0, 1);
@@ -3150,84 +2981,6 @@ int mcs_ba_point_block_eval(int32_t device, const double* H, double lambda, cons
   B.down(Y, dY, 18 * N);
   if (B.err != hipSuccess) { set_hip_error(B.err, "point_block_eval download", __FILE__, __LINE__); return MCS_ERR_HIP; }
   return MCS_OK;
-}
-
-int mcs_ldlt_set_wait_ticks(int64_t ticks) {
-  ldlt::set_wait_ticks((long long)ticks);
-  return MCS_OK;
-}
-
-int mcs_dense_ldlt_solve(int32_t device, const double* S, int32_t n, const double* b, double* x,
-                         int32_t* zero_pivot) {
-  return mcs_dense_ldlt_solve_ex(device, S, n, b, x, zero_pivot, 0);
-}
-
-int mcs_dense_ldlt_solve_ex(int32_t device, const double* S, int32_t n, const double* b, double* x,
-                            int32_t* zero_pivot, int32_t path) {
-  if (!S || !b || !x || n < 1 || path < 0 || path > 3) return MCS_ERR_ARG;
-  if (int rc = host::open_device(device, "dense_ldlt_solve")) return rc;
-  const int T = ldlt::tiles_for(n);
-  const size_t NT = ldlt::tile_doubles(T), Np = (size_t)ldlt::TB * T;
-  // path 0: the tile band of S (the widest tile diagonal holding a non-zero), as the BA derives
-  // it from its structure; the other paths factor densely
-  int band = T;
-  if (path == 0 && T > 1) {
-    int w = 1;
-    for (int r = 0; r < n; r++)
-      for (int c = 0; c < r; c++)
-        if (S[(size_t)r * n + c] != 0.0) { w = std::max(w, r / ldlt::TB - c / ldlt::TB); break; }
-    band = ldlt::pipe_band(T, w + 1);
-  }
-  const bool pipelined = path != 3 && T >= 2 && ldlt::pipe_supported(T, band);
-  if (!pipelined && T > 1 && (size_t)T * ldlt::TB * 8 > 96 * 1024) return MCS_ERR_UNSUPPORTED;
-  std::vector<double> hA(NT, 0.0), hb(Np, 0.0);
-  for (int r = 0; r < n; r++)
-    for (int c = 0; c <= r; c++) hA[ldlt::sidx(r, c, T)] = S[(size_t)r * n + c];
-  for (int r = 0; r < n; r++) hb[r] = b[r];
-  host::DevBufs B;
-  double *dA = B.alloc<double>(NT), *dL = B.alloc<double>(NT), *dI = B.alloc<double>((size_t)T * 4096);
-  double *db = B.alloc<double>(Np), *dx = B.alloc<double>(Np), *dz = B.alloc<double>(Np);
-  int* dflag = B.alloc<int>(4);
-  hipStream_t st = nullptr;
-  int rc = MCS_OK;
-  auto chk = [&](hipError_t e, const char* what) {
-    if (e != hipSuccess && rc == MCS_OK) { set_hip_error(e, what, __FILE__, __LINE__); rc = MCS_ERR_HIP; }
-  };
-  chk(B.err, "malloc");
-  chk(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "stream");
-  if (rc == MCS_OK) {
-    chk(hipMemcpyAsync(dA, hA.data(), NT * 8, hipMemcpyHostToDevice, st), "h2d");
-    chk(hipMemcpyAsync(db, hb.data(), Np * 8, hipMemcpyHostToDevice, st), "h2d");
-    chk(hipMemsetAsync(dflag, 0, 4, st), "memset");
-    if (T == 1 && path == 0) {
-      chk(ldlt::solve_one_tile(dA, db, dx, n, 1.0, dflag, st), "ldlt");
-    } else {
-      chk(ldlt::pad(dA, db, n, T, 1.0, st), "pad");
-      ldlt::Work w{dL, dI, dz};
-      // path 0 (banded) and 2 (dense): the pipelined factorisation (one launch); path 1: one
-      // launch per step; all with the multi-workgroup backward substitution.  Path 3, and a
-      // system the pipeline does not take (as in the BA): one launch per step + the
-      // one-workgroup backward substitution, without the pipeline's sync words.
-      if (rc == MCS_OK && pipelined) chk(ldlt::pipe_prepare(w, T, st, path == 0 ? band : 0), "pipe_prepare");
-      w.per_step = (path == 1);
-      chk(ldlt::solve(dA, db, dx, T, w, dflag, st), "ldlt");
-      chk(hipStreamSynchronize(st), "sync");
-      ldlt::pipe_release(w);
-    }
-    std::vector<double> hx(Np);
-    int32_t fl = 0;
-    chk(hipMemcpyAsync(hx.data(), dx, Np * 8, hipMemcpyDeviceToHost, st), "d2h");
-    chk(hipMemcpyAsync(&fl, dflag, 4, hipMemcpyDeviceToHost, st), "d2h");
-    chk(hipStreamSynchronize(st), "sync");
-    for (int r = 0; r < n; r++) x[r] = hx[r];
-    if (rc == MCS_OK && (fl & ldlt::kFlagTimeout)) {
-      set_error("dense LDL^T: a hand-off wait of the pipelined solve timed out; x discarded");
-      rc = MCS_ERR_HIP;
-    }
-    if (zero_pivot) *zero_pivot = fl & ldlt::kFlagZeroPivot;
-  }
-  if (st) (void)hipStreamDestroy(st);   // the buffers go with B
-  return rc;
 }
 
 }  // extern "C"

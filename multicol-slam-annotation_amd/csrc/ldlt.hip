@@ -15,6 +15,8 @@
 //                      the right-hand side b_i -= L_ik u_k.
 // backward (one workgroup): x_k = Linv_kk^T z_k, z_j -= L_kj^T x_k for j < k.
 #include "ldlt.hpp"
+#include "host_util.hpp"
+#include "../../include/mcs_ba.h"
 #include <atomic>
 #include <map>
 #include <mutex>
@@ -1350,3 +1352,88 @@ hipError_t pad(double* A, double* b, int n, int T, double diag_value, hipStream_
 
 }  // namespace ldlt
 }  // namespace mcs
+
+// ---- C entries (include/mcs_ba.h): the dense solve on its own, and the wait-bound test hook
+using namespace mcs;
+
+extern "C" {
+
+int mcs_ldlt_set_wait_ticks(int64_t ticks) {
+  ldlt::set_wait_ticks((long long)ticks);
+  return MCS_OK;
+}
+
+int mcs_dense_ldlt_solve(int32_t device, const double* S, int32_t n, const double* b, double* x,
+                         int32_t* zero_pivot) {
+  return mcs_dense_ldlt_solve_ex(device, S, n, b, x, zero_pivot, 0);
+}
+
+int mcs_dense_ldlt_solve_ex(int32_t device, const double* S, int32_t n, const double* b, double* x,
+                            int32_t* zero_pivot, int32_t path) {
+  if (!S || !b || !x || n < 1 || path < 0 || path > 3) return MCS_ERR_ARG;
+  if (int rc = host::open_device(device, "dense_ldlt_solve")) return rc;
+  const int T = ldlt::tiles_for(n);
+  const size_t NT = ldlt::tile_doubles(T), Np = (size_t)ldlt::TB * T;
+  // path 0: the tile band of S (the widest tile diagonal holding a non-zero), as the BA derives
+  // it from its structure; the other paths factor densely
+  int band = T;
+  if (path == 0 && T > 1) {
+    int w = 1;
+    for (int r = 0; r < n; r++)
+      for (int c = 0; c < r; c++)
+        if (S[(size_t)r * n + c] != 0.0) { w = std::max(w, r / ldlt::TB - c / ldlt::TB); break; }
+    band = ldlt::pipe_band(T, w + 1);
+  }
+  const bool pipelined = path != 3 && T >= 2 && ldlt::pipe_supported(T, band);
+  if (!pipelined && T > 1 && (size_t)T * ldlt::TB * 8 > 96 * 1024) return MCS_ERR_UNSUPPORTED;
+  std::vector<double> hA(NT, 0.0), hb(Np, 0.0);
+  for (int r = 0; r < n; r++)
+    for (int c = 0; c <= r; c++) hA[ldlt::sidx(r, c, T)] = S[(size_t)r * n + c];
+  for (int r = 0; r < n; r++) hb[r] = b[r];
+  host::DevBufs B;
+  double *dA = B.alloc<double>(NT), *dL = B.alloc<double>(NT), *dI = B.alloc<double>((size_t)T * 4096);
+  double *db = B.alloc<double>(Np), *dx = B.alloc<double>(Np), *dz = B.alloc<double>(Np);
+  int* dflag = B.alloc<int>(4);
+  hipStream_t st = nullptr;
+  int rc = MCS_OK;
+  auto chk = [&](hipError_t e, const char* what) {
+    if (e != hipSuccess && rc == MCS_OK) { set_hip_error(e, what, __FILE__, __LINE__); rc = MCS_ERR_HIP; }
+  };
+  chk(B.err, "malloc");
+  chk(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "stream");
+  if (rc == MCS_OK) {
+    chk(hipMemcpyAsync(dA, hA.data(), NT * 8, hipMemcpyHostToDevice, st), "h2d");
+    chk(hipMemcpyAsync(db, hb.data(), Np * 8, hipMemcpyHostToDevice, st), "h2d");
+    chk(hipMemsetAsync(dflag, 0, 4, st), "memset");
+    if (T == 1 && path == 0) {
+      chk(ldlt::solve_one_tile(dA, db, dx, n, 1.0, dflag, st), "ldlt");
+    } else {
+      chk(ldlt::pad(dA, db, n, T, 1.0, st), "pad");
+      ldlt::Work w{dL, dI, dz};
+      // path 0 (banded) and 2 (dense): the pipelined factorisation (one launch); path 1: one
+      // launch per step; all with the multi-workgroup backward substitution.  Path 3, and a
+      // system the pipeline does not take (as in the BA): one launch per step + the
+      // one-workgroup backward substitution, without the pipeline's sync words.
+      if (rc == MCS_OK && pipelined) chk(ldlt::pipe_prepare(w, T, st, path == 0 ? band : 0), "pipe_prepare");
+      w.per_step = (path == 1);
+      chk(ldlt::solve(dA, db, dx, T, w, dflag, st), "ldlt");
+      chk(hipStreamSynchronize(st), "sync");
+      ldlt::pipe_release(w);
+    }
+    std::vector<double> hx(Np);
+    int32_t fl = 0;
+    chk(hipMemcpyAsync(hx.data(), dx, Np * 8, hipMemcpyDeviceToHost, st), "d2h");
+    chk(hipMemcpyAsync(&fl, dflag, 4, hipMemcpyDeviceToHost, st), "d2h");
+    chk(hipStreamSynchronize(st), "sync");
+    for (int r = 0; r < n; r++) x[r] = hx[r];
+    if (rc == MCS_OK && (fl & ldlt::kFlagTimeout)) {
+      set_error("dense LDL^T: a hand-off wait of the pipelined solve timed out; x discarded");
+      rc = MCS_ERR_HIP;
+    }
+    if (zero_pivot) *zero_pivot = fl & ldlt::kFlagZeroPivot;
+  }
+  if (st) (void)hipStreamDestroy(st);   // the buffers go with B
+  return rc;
+}
+
+}  // extern "C"

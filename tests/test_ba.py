@@ -232,6 +232,28 @@ def test_gpu_device_driven_lm_matches_host_driven(gpu, which, problem, small_pro
 
 
 @pytest.mark.gpu
+def test_gpu_long_trace_selects_host_driven_loop(gpu, small_problem):
+    """The driver selection by trace length: a caller asking for more than the device loop's 64
+    trace entries of a run allowed more than 64 iterations gets the host-driven loop, one asking
+    for 64 the device-driven one.  Same controller, so the same decisions; the trial sums are
+    added in another order, so values agree to rounding."""
+    from mcs_amd import ba
+    S = ba.Solver()
+    o = ba.BAOptions(max_iterations=80)
+    h = S.optimize(small_problem, options=o, trace=80)
+    d = S.optimize(small_problem, options=o, trace=64)
+    hr, dr = h["report"], d["report"]
+    assert hr.iterations == dr.iterations and hr.stop_flag == dr.stop_flag
+    assert (hr.n_active_edges, hr.n_active_poses, hr.n_active_points) == \
+        (dr.n_active_edges, dr.n_active_poses, dr.n_active_points)
+    assert abs(dr.chi2_final - hr.chi2_final) <= 1e-9 * hr.chi2_final
+    assert len(h["trace"]) == hr.iterations and len(d["trace"]) == dr.iterations
+    assert hr.iterations > 0
+    m = min(len(h["trace"]), len(d["trace"]))
+    assert np.all(np.abs(d["trace"][:m] - h["trace"][:m]) <= 1e-9 * np.abs(h["trace"][:m]))
+
+
+@pytest.mark.gpu
 def test_gpu_local_ba_bitwise_reproducible(gpu, problem):
     """Device-driven LocalBA twice: the arrival counter and every sum order are fixed, so the
     results are the same bits."""

@@ -4,7 +4,7 @@ of the model decrease separately, g2o sums the whole update vector in one index-
 g2o: OptimizationAlgorithmLevenberg::computeScale
 (/root/reference/ThirdParty/g2o/g2o/core/optimization_algorithm_levenberg.cpp:182-189),
 scale = sum_j x_j (lambda x_j + b_j), then rho = (currentChi - tempChi) / (scale + 1e-3)
-(:128-131).  The product (csrc/ba.hip lm_control) adds a poses' partial sum and a points'
+(:128-131).  The product (csrc/lm_control.hpp lm_step) adds a poses' partial sum and a points'
 partial sum, each reduced in parallel.
 
 The bound (stated in DESIGN.md §3.5): every summation order of n terms t_j lands within

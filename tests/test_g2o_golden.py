@@ -9,9 +9,11 @@ failures in a row, stalls that trip Raul's nBad stop and the terminate action's 
 
 The product's device code is replayed on the same scripted inputs through test hooks that call
 the production device functions (mcs_ba_lm_replay -> lm_start_body / lm_lambda0_body /
-lm_control, mcs_ba_huber_eval -> huber, csrc/ba.hip) and must reproduce every lambda, nu and
-accept / reject decision bit for bit, the number of trials and iterations each optimize() call
-runs, the terminate action's stop flag, and the Huber rho / rho' values.
+lm_step of csrc/lm_control.hpp, mcs_ba_huber_eval -> huber, csrc/ba.hip) and must reproduce
+every lambda, nu and accept / reject decision bit for bit, the number of trials and iterations
+each optimize() call runs, the terminate action's stop flag, and the Huber rho / rho' values.
+The LM controller is plain C++ shared by the device-driven and the host-driven loop; its host
+compile (tests/cpp/lm_replay_host.cpp) is held to the same scenarios without a GPU.
 """
 import ctypes
 import os
@@ -50,23 +52,21 @@ def test_golden_structure(gold):
     assert int(meta[:, 0].sum()) == 446 and np.any(meta[:, 2] == 1) and np.any(meta[:, 2] == 0)
 
 
-@pytest.mark.gpu
-def test_gpu_lm_control_replays_reference(gpu, gold):
-    import mcs_amd
+def check_lm_replay(gold, replay):
+    """replay(options, in3, trials, out[n][10]) -> trials run.  Every lambda, nu and accept /
+    reject decision bit for bit, the trial count, iterations, done and the terminate action's
+    stop flag, over all 60 scenarios."""
     from mcs_amd import ba
-    L = mcs_amd.lib()
     ins, trials, outs, meta = gold["lm_in"], gold["lm_trials"], gold["lm_out"], gold["lm_meta"]
+    assert len(ins) == 60
     for s in range(len(ins)):
         n_ref, it_ref, stop_ref, max_it = (int(v) for v in meta[s])
         o = ba.BAOptions(max_iterations=max_it, gain_threshold=1e-6, terminate_max_iter=15,
                          max_trials=10, tau=1e-5)
         tr = np.ascontiguousarray(trials[s])
         out = np.zeros((len(tr), 10))
-        n = ctypes.c_int32()
-        rc = L.mcs_ba_lm_replay(0, ctypes.byref(o), ba._p(np.ascontiguousarray(ins[s])), ba._p(tr), len(tr),
-                                ba._p(out), ctypes.byref(n))
-        assert rc == 0
-        assert n.value == n_ref, s
+        n = replay(o, np.ascontiguousarray(ins[s]), tr, out)
+        assert n == n_ref, s
         ref = outs[s][:n_ref]
         got = out[:n_ref]
         assert np.array_equal(got[:, 0], ref[:, 0]), (s, "lambda used")
@@ -76,6 +76,39 @@ def test_gpu_lm_control_replays_reference(gpu, gold):
         assert int(got[-1, 6]) == it_ref, (s, "iterations")
         assert int(got[-1, 7]) == 1, (s, "done")
         assert int(got[-1, 8]) == stop_ref, (s, "terminate action stop flag")
+
+
+@pytest.mark.gpu
+def test_gpu_lm_control_replays_reference(gpu, gold):
+    import mcs_amd
+    from mcs_amd import ba
+    L = mcs_amd.lib()
+
+    def replay(o, in3, tr, out):
+        n = ctypes.c_int32()
+        rc = L.mcs_ba_lm_replay(0, ctypes.byref(o), ba._p(in3), ba._p(tr), len(tr), ba._p(out), ctypes.byref(n))
+        assert rc == 0
+        return n.value
+
+    check_lm_replay(gold, replay)
+
+
+def test_cpu_lm_control_replays_reference(gold, tmp_path):
+    """The same controller text (csrc/lm_control.hpp) compiled for the host: the one the
+    host-driven loop of Optimizer::run, and with it every sharded GlobalBA, runs."""
+    import subprocess
+    from mcs_amd import ba
+    so = str(tmp_path / "liblm_replay_host.so")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC",
+                           os.path.join(HERE, "cpp", "lm_replay_host.cpp"), "-o", so])
+    fn = ctypes.CDLL(so).lm_replay_host
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p]
+
+    def replay(o, in3, tr, out):
+        return fn(ctypes.addressof(o), ba._p(in3), ba._p(tr), len(tr), ba._p(out))
+
+    check_lm_replay(gold, replay)
 
 
 @pytest.mark.gpu
