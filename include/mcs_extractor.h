@@ -109,7 +109,8 @@ int mcs_extractor_set_masks_device(mcs_extractor* h, const uint8_t* d_masks, int
                                    void* stream);
 
 /* Batch, device-resident (HBM in, HBM out), asynchronous on `stream` (hipStream_t, NULL =
- * default).  d_images: n_frames x height x width (pitch = width).  d_mask_index: per
+ * default).  d_images: n_frames x height x width (pitch = width), 4-byte aligned when width is
+ * a multiple of 4 (MCS_ERR_ARG otherwise; any address for other widths).  d_mask_index: per
  * frame index into the registered masks, or NULL => mask 0 if masks are registered, no
  * mask otherwise.  Outputs: d_kps [n_frames][cap], d_counts [n_frames],
  * d_desc [n_frames][cap][desc_size], cap = mcs_extractor_capacity(). */

@@ -43,7 +43,7 @@ struct mcs_extractor {
   int32_t* d_xofs = nullptr; int16_t* d_alpha = nullptr;
   int32_t* d_yofs = nullptr; int16_t* d_beta = nullptr;
   mcs::CellDesc* d_cells = nullptr;
-  mcs::FastUnit* d_units = nullptr;
+  mcs::FastWave* d_units = nullptr;
   // workspace
   uint8_t* d_pyr = nullptr;      // [F][pyr_frame_bytes]   raw levels 1..L-1 (pitch align64)
   uint8_t* d_blur = nullptr;     // [F][img_frame_bytes]   blurred levels 0..L-1
@@ -55,7 +55,7 @@ struct mcs_extractor {
   int32_t* d_sel_count = nullptr;  // [F][nlevels]
   // masks: registered set + single-call slot, each with per-cell window bitmaps
   uint8_t* d_mask_pyr = nullptr; int n_masks = 0;
-  mcs::FastUnit* d_munits = nullptr; int64_t munit_stride = 0;   // per-mask FAST units
+  mcs::FastWave* d_munits = nullptr; int64_t munit_stride = 0;   // per-mask FAST waves
   uint8_t* d_mask_single = nullptr;
   // k_pyr_rows unit tables (pyr_units.hpp), one per batch-size class and kind, built on first
   // use: full = every pixel (no registered mask, the single-call path, dBRIEF / mdBRIEF, whose
@@ -147,6 +147,12 @@ static int run_batch(mcs_extractor* h, const uint8_t* d_images, int F, const uin
   const Plan& pl = h->plan;
   const int nl = pl.nlevels;
   const int64_t img0_fs = (int64_t)pl.W * pl.H;
+  // the FAST waves of level 0 are packed for dword-aligned rows when W is a multiple of 4
+  // (fast_run_lanes: no spare lane for a row's byte offset)
+  if (pl.W % 4 == 0 && ((uintptr_t)d_images & 3) != 0) {
+    set_error("images must be 4-byte aligned when the width is a multiple of 4");
+    return MCS_ERR_ARG;
+  }
   // registered masks (not the single-call slot) drive both the FAST and the pyramid unit lists
   const bool per_mask = mask_pyr && mask_pyr == h->d_mask_pyr && h->d_munits;
   const bool orb = !pl.p.learn_masks && !pl.p.do_dbrief;
@@ -225,7 +231,7 @@ static int run_batch(mcs_extractor* h, const uint8_t* d_images, int F, const uin
   {
     FastRowArgs fl = fa;
     fl.units = per_mask ? h->d_munits : h->d_units;
-    fl.nunits = per_mask ? (int)h->munit_stride : (int)pl.fast_units.size();
+    fl.nunits = per_mask ? (int)h->munit_stride : (int)pl.fast_waves.size();
     fl.unit_mstride = per_mask ? h->munit_stride : 0;
     launch_fast_rows(fl, st);   // also zeroes d_counts
   }
@@ -323,7 +329,7 @@ int mcs_extractor_create(const mcs_extractor_params* p, int32_t width, int32_t h
   ALLOC(h->d_yofs, pl.yofs.size());
   ALLOC(h->d_beta, pl.beta.size());
   ALLOC(h->d_cells, pl.cells.size());
-  ALLOC(h->d_units, pl.fast_units.size());
+  ALLOC(h->d_units, pl.fast_waves.size());
   ALLOC(h->d_pyr, F * pl.pyr_frame_bytes);
   ALLOC(h->d_blur, F * pl.img_frame_bytes);
   ALLOC(h->d_slots, F * pl.slots_per_frame);
@@ -345,7 +351,7 @@ int mcs_extractor_create(const mcs_extractor_params* p, int32_t width, int32_t h
   if (e == hipSuccess) e = hipMemcpy(h->d_yofs, pl.yofs.data(), pl.yofs.size() * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(h->d_beta, pl.beta.data(), pl.beta.size() * 2, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(h->d_cells, pl.cells.data(), pl.cells.size() * sizeof(CellDesc), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(h->d_units, pl.fast_units.data(), pl.fast_units.size() * sizeof(FastUnit), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(h->d_units, pl.fast_waves.data(), pl.fast_waves.size() * sizeof(FastWave), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     set_hip_error(e, "upload plan tables", __FILE__, __LINE__);
     mcs_extractor_destroy(h);
@@ -446,23 +452,24 @@ int mcs_extractor_set_masks_device(mcs_extractor* h, const uint8_t* d_masks, int
   std::vector<uint8_t> hm((size_t)n_masks * pl.mask_frame_bytes);
   MCS_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
   MCS_HIP_CHECK(hipMemcpy(hm.data(), h->d_mask_pyr, hm.size(), hipMemcpyDeviceToHost));
-  std::vector<std::vector<FastUnit>> lists(n_masks);
+  std::vector<std::vector<FastWave>> lists(n_masks);
   std::vector<PyrNeed> need(n_masks);
   size_t stride = 0;
   for (int m = 0; m < n_masks; m++) {
-    std::vector<FastUnit> dead;
-    build_masked_units(pl, hm.data() + (size_t)m * pl.mask_frame_bytes, lists[m], dead);
+    std::vector<FastUnit> live, dead;
+    build_masked_units(pl, hm.data() + (size_t)m * pl.mask_frame_bytes, live, dead);
     // what the pyramid has to compute for frames of this mask (pyr_units.hpp)
-    build_pyr_need(pl, hm.data() + (size_t)m * pl.mask_frame_bytes, lists[m], need[m]);
-    lists[m].insert(lists[m].end(), dead.begin(), dead.end());   // heavy units first
+    build_pyr_need(pl, hm.data() + (size_t)m * pl.mask_frame_bytes, live, need[m]);
+    live.insert(live.end(), dead.begin(), dead.end());   // heavy units first
+    pack_fast_units(pl, live, lists[m]);
     stride = std::max(stride, lists[m].size());
   }
   stride = std::max<size_t>(stride, 1);
-  FastUnit pad{};   // no cells, no rows: the wave exits without a store
-  std::vector<FastUnit> all((size_t)n_masks * stride, pad);
+  FastWave pad{};   // no cells, no rows: the wave exits without a store
+  std::vector<FastWave> all((size_t)n_masks * stride, pad);
   for (int m = 0; m < n_masks; m++) std::copy(lists[m].begin(), lists[m].end(), all.begin() + (size_t)m * stride);
   if ((rc = dalloc(&h->d_munits, all.size())) != MCS_OK) return rc;
-  MCS_HIP_CHECK(hipMemcpy(h->d_munits, all.data(), all.size() * sizeof(FastUnit), hipMemcpyHostToDevice));
+  MCS_HIP_CHECK(hipMemcpy(h->d_munits, all.data(), all.size() * sizeof(FastWave), hipMemcpyHostToDevice));
   h->munit_stride = (int64_t)stride;
   h->n_masks = n_masks;
   h->pyr_need.swap(need);

@@ -53,14 +53,14 @@ void launch_pyr_blur(const PyrArgs& a, bool resize, bool wide, hipStream_t st);
 
 void launch_mask_pyramids(const Plan& pl, const uint8_t* d_masks, int n, uint8_t* dst,
                           hipStream_t st);
-// ---- K2: FAST over runs of cells (row-streaming), one wave per FastUnit
+// ---- K2: FAST over runs of cells (row-streaming), one wave per FastWave (one or two runs)
 struct FastRowArgs {
   const uint8_t* img0; int64_t img0_fstride;
   const uint8_t* pyr; int64_t pyr_fstride;
   const uint8_t* mask_pyr; int64_t mask_fstride;  // mask pyramids (nullable = no mask)
   const int32_t* mask_index; int nmasks;           // index clamped to [0, nmasks)
-  const FastUnit* units; int nunits;
-  int64_t unit_mstride;   // per-mask unit lists (build_masked_units): units of mask m at
+  const FastWave* units; int nunits;
+  int64_t unit_mstride;   // per-mask unit lists (pack_fast_units): units of mask m at
                           // units + m * unit_mstride; 0 = one list for every frame
   const CellDesc* cells; int ncells;
   uint32_t* slots; int64_t slots_fstride;

@@ -83,7 +83,81 @@ void zero_runs(const std::vector<CellDesc>& cells, int c, int e, int level, int 
   }
 }
 
+FastRun make_run(const std::vector<CellDesc>& cells, int a, int b) {
+  FastRun r;
+  r.wy0 = cells[a].wy0;
+  r.ux0 = cells[a].wx0; r.ux1 = cells[b - 1].wx1;
+  r.ncells = (int16_t)(b - a);
+  r.cell0 = a;
+  return r;
+}
+
 }  // namespace
+
+int fast_run_lanes(const Plan& pl, int level, int ux0, int ux1) {
+  const int xa = (ux0 - 3) & ~3;
+  return (ux1 + 3 - xa + 3) / 4 + (pl.lv[level].pitch % 4 != 0 ? 1 : 0);
+}
+
+void pack_fast_units(const Plan& pl, const std::vector<FastUnit>& units, std::vector<FastWave>& out) {
+  const std::vector<CellDesc>& cells = pl.cells;
+  auto lanes = [&](int level, int a, int b) {
+    return fast_run_lanes(pl, level, cells[a].wx0, cells[b - 1].wx1);
+  };
+  // the longest run [a, b) of cells from a, b <= e, that fits `room` lanes (b == a: none)
+  auto take = [&](int level, int a, int e, int room) {
+    int b = a;
+    while (b < e && lanes(level, a, b + 1) <= room) b++;
+    return b;
+  };
+  auto open_wave = [&](const FastUnit& u, int wh, const FastRun& r0) {
+    FastWave w;
+    w.level = u.level; w.wcell = u.wcell; w.wh = (int16_t)wh; w.split = kFastWaveLanes;
+    w.r[0] = r0;
+    w.r[1] = r0; w.r[1].ncells = 0; w.r[1].ux1 = r0.ux0;
+    out.push_back(w);
+  };
+  int open = -1, used = 0;   // a wave of one run that may still take a second one; its lanes
+  for (size_t i = 0; i < units.size();) {
+    const FastUnit& u = units[i];
+    if (u.wy1 <= u.wy0) {   // count-zeroing unit (or a pad): as it is
+      FastRun r;
+      r.wy0 = u.wy0; r.ux0 = u.ux0; r.ux1 = u.ux1;
+      r.ncells = u.ncells; r.cell0 = u.cell0;
+      open_wave(u, 0, r);
+      open = -1;
+      i++;
+      continue;
+    }
+    // the live range [c, e) of the cell row: its runs, which follow each other
+    size_t j = i;
+    int e = u.cell0;
+    while (j < units.size() && units[j].level == u.level && units[j].wy0 == u.wy0 &&
+           units[j].wy1 == u.wy1 && units[j].cell0 == e) { e += units[j].ncells; j++; }
+    int c = u.cell0;
+    const int wh = u.wy1 - u.wy0;
+    // a second run needs its rows at the first run's byte offset within a dword (the kernel
+    // shifts a wave's row by one uniform amount): any two on a level with dword-aligned rows
+    if (open >= 0 && out[open].level == u.level && out[open].wh == wh &&
+        (u.wy0 - out[open].r[0].wy0) * pl.lv[u.level].pitch % 4 == 0) {
+      const int b = take(u.level, c, e, kFastWaveLanes - used);
+      if (b > c) {
+        out[open].split = (int16_t)used;
+        out[open].r[1] = make_run(cells, c, b);
+        c = b;
+      }
+    }
+    open = -1;
+    while (c < e) {
+      const int b = take(u.level, c, e, kFastWaveLanes);
+      open_wave(u, wh, make_run(cells, c, b));
+      used = lanes(u.level, c, b);
+      open = used < kFastWaveLanes ? (int)out.size() - 1 : -1;   // the row's last wave stays open
+      c = b;
+    }
+    i = j;
+  }
+}
 
 int build_plan(const mcs_extractor_params& p, int W, int H, Plan& pl) {
   if (W <= 0 || H <= 0 || p.nlevels < 1 || p.nlevels > kMaxLevels || p.nfeatures < 0 ||
@@ -248,6 +322,8 @@ int build_plan(const mcs_extractor_params& p, int W, int H, Plan& pl) {
     sel += cap;
   }
   for (int l = p.nlevels; l <= kMaxLevels; l++) pl.unit_begin[l] = (int32_t)pl.fast_units.size();
+  pl.fast_waves.clear();
+  pack_fast_units(pl, pl.fast_units, pl.fast_waves);
   pl.pyr_frame_bytes = pyr_off;
   pl.img_frame_bytes = img_off;
   pl.mask_frame_bytes = mask_off;

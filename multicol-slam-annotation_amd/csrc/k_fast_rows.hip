@@ -1,5 +1,8 @@
 // K2, row-streaming form: FAST-9/16 + cell-local 3x3 non-max suppression + runByPixelsMask
-// over a run of consecutive cells of one cell row (FastUnit), one wave per run.
+// over runs of consecutive cells of one cell row, one wave per one or two runs (FastWave): the
+// runs sit side by side in the wave's lanes and in its 256-byte window rows, each with its own
+// +-3 px halo, so the loads, the compass and the exact test do not know of them; only the
+// per-lane addresses, the detection mask and phase C (a corner's run by its window column) do.
 //
 // Reference: ComputeKeyPointsOctTree src/mdBRIEFextractorOct.cpp:874-949, which runs
 // FastFeatureDetector(th, nonmax, TYPE_9_16)::detect on every 30 px cell ROI (OpenCV semantics
@@ -73,9 +76,9 @@ constexpr int kScoreRows = kBand + 3;
 // then their lists (carried corners, then the band's survivors, compacted in place into its
 // corners)
 constexpr int kRingBytes = (kBand + 6) * 256, kScoreBytes = kScoreRows * 256;
-// a run's detection span is <= 246 px (kFastUnitSpan - 6): <= 246 carried corners + 246 kBand
-// survivors
-constexpr int kListCap = 248 + kBand * 248;
+// a wave's detection pixels are < 256 per row (64 lanes x 4 px less the runs' halos): < 256
+// carried corners + 256 kBand survivors
+constexpr int kListCap = 256 + kBand * 256;
 constexpr int kScoreBase = 4 * kRingBytes, kListBase = kScoreBase + 4 * kScoreBytes;
 constexpr int kLdsBytes = kListBase + 4 * 2 * (kListCap + 2);   // + a dummy slot per list
 
@@ -155,47 +158,79 @@ __global__ __launch_bounds__(256) void k_fast_rows(FastRowArgs a) {
   // prove them unclobbered), which cost 0.1 ms per step
   auto zero_count = [&] { if (ui == 0 && lane == 0) a.frame_count[f] = 0; };
   const int mi = a.mask_index ? min(max(a.mask_index[f], 0), a.nmasks - 1) : 0;
-  const FastUnit u = a.units[(int64_t)mi * a.unit_mstride + ui];
+  const FastWave u = a.units[(int64_t)mi * a.unit_mstride + ui];
   FP_BEGIN();
-  const int level = u.level, nc = u.ncells, wh = u.wy1 - u.wy0;
-  int32_t* const cnt_out = a.cell_counts + (int64_t)f * a.ncells + u.cell0;
+  const int level = u.level, wh = u.wh;
+  // lane k: cell k of the wave's cells, run 1's after run 0's
+  const int ncA = u.r[0].ncells, nc = ncA + u.r[1].ncells;
+  const int cell_l = lane < ncA ? u.r[0].cell0 + lane : u.r[1].cell0 + (lane - ncA);
+  int32_t* const cnt_out = a.cell_counts + (int64_t)f * a.ncells;
   if (wh <= 0) {
-    if (lane < nc) cnt_out[lane] = 0;
+    if (lane < nc) cnt_out[cell_l] = 0;
     zero_count();
     return;
   }
-  // mask rows of the run (the level of the frame's mask pyramid, pitch bpitch: aligned dwords)
-  const uint8_t* const mrow0 =
-      a.mask_pyr ? a.mask_pyr + (int64_t)mi * a.mask_fstride +
-                       a.lp.mask_off[level] + (int64_t)(u.wy0 - 3) * a.lp.bpitch[level] + u.xa
-                 : nullptr;
+  // The wave's window: column x (0..255) of its 256 byte rows belongs to lane x / 4, and to
+  // run 1 from column 4 * split on.  Column x is level column xo + x and window row y_rel level
+  // row wy0 - 3 + y_rel of the column's run.
+  const int split = u.split, split4 = 4 * split;
+  const bool in_b = lane >= split;
+  const int xoA = (u.r[0].ux0 - 3) & ~3, xoB = ((u.r[1].ux0 - 3) & ~3) - split4;
+  const int xl = (in_b ? xoB : xoA) + 4 * lane;              // the lane's first level column
   const int mpitch = a.lp.bpitch[level];
   const int t = a.threshold;
-  const int xa = u.xa, wc = u.wcell, span = u.ux1 - u.ux0;
+  const int wc = u.wcell;
   const uint32_t magic = 65536u / (uint32_t)wc + 1u;   // cx / wc for cx < 256, wc <= 64
   const int pitch = a.lp.pitch[level];
   const uint8_t* const img = (level == 0) ? a.img0 + (int64_t)f * a.img0_fstride
                                           : a.pyr + (int64_t)f * a.pyr_fstride + a.lp.pyr_off[level];
-  const uint8_t* const row0 = img + (int64_t)(u.wy0 - 3) * pitch + xa;
-  // raw rows y_rel in [0, wh + 6); detection rows [3, wh + 3)
+  // raw rows y_rel in [0, wh + 6); detection rows [3, wh + 3).  Row y_rel of the wave starts at
+  // row0 + y_rel * pitch for run 0's lanes; run 1's rows lie a whole number of dwords behind
+  // them (its cell row follows run 0's, and the planner pairs only rows whose bytes sit alike in
+  // their dwords), so a lane's dword is one uniform row address plus the lane's constant byte
+  // offset lb, and the row's byte shift is uniform
+  const int dy = u.r[1].wy0 - u.r[0].wy0;
+  const uint8_t* const row0 = img + (int64_t)(u.r[0].wy0 - 3) * pitch + xoA;
+  const uint32_t lb = 4u * (uint32_t)lane + (in_b ? (uint32_t)(dy * pitch + xoB - xoA) : 0u);
+  // mask rows (the level of the frame's mask pyramid, pitch bpitch: aligned dwords)
+  const uint8_t* const mrow0 =
+      a.mask_pyr ? a.mask_pyr + (int64_t)mi * a.mask_fstride +
+                       a.lp.mask_off[level] + (int64_t)(u.r[0].wy0 - 3) * mpitch + xoA
+                 : nullptr;
+  const uint32_t mlb = 4u * (uint32_t)lane + (in_b ? (uint32_t)(dy * mpitch + xoB - xoA) : 0u);
 
-  // top bit of byte k: pixel xa + 4 lane + k is a detection pixel of the run
+  // top bit of byte k: level column xl + k is a detection pixel of the lane's run
   uint32_t detm = 0;
+  {
+    const int ux0l = in_b ? u.r[1].ux0 : u.r[0].ux0, ux1l = in_b ? u.r[1].ux1 : u.r[0].ux1;
 #pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const int x = xa + 4 * lane + k;
-    detm |= (x >= u.ux0 && x < u.ux1) ? (0x80u << (8 * k)) : 0u;
+    for (int k = 0; k < 4; k++) {
+      const int x = xl + k;
+      detm |= (x >= ux0l && x < ux1l) ? (0x80u << (8 * k)) : 0u;
+    }
   }
-  const int slot_off = lane < nc ? a.cells[u.cell0 + lane].slot_off : 0;   // lane k: cell k
+  const int slot_off = lane < nc ? a.cells[cell_l].slot_off : 0;   // lane k: cell k
   uint32_t* const outf = a.slots + (int64_t)f * a.slots_fstride;
-  int cnt = 0;                                                            // lane k: cell k
+  int cnt = 0;                                                    // lane k: cell k
+  // phase C takes these by the run of a corner's column: cell-row column cx = cxo + x, the
+  // detection span, and the packed (x - kMinBorder) | (y - kMinBorder) << 12 of (x, y_rel) = 0
+  const int cxoA = xoA - u.r[0].ux0, cxoB = xoB - u.r[1].ux0;
+  const int spanA = u.r[0].ux1 - u.r[0].ux0, spanB = u.r[1].ux1 - u.r[1].ux0;
+  const int recA = (xoA - kMinBorder) + ((u.r[0].wy0 - 3 - kMinBorder) << 12);
+  const int recB = (xoB - kMinBorder) + ((u.r[1].wy0 - 3 - kMinBorder) << 12);
 
-  // raw row r (y_rel) of the run: one aligned dword per lane, the row's byte offset undone by
-  // alignbyte with the next lane's dword (lane 63 is never consumed)
+  // raw row r (y_rel): one aligned dword per lane, the row's byte offset undone by alignbyte
+  // with the next lane's dword (on a level with such offsets every run has a lane to spare
+  // behind its last pixel's: FastWave)
   // No clamping: the last prefetch reaches at most 3 rows past the run's raw rows (row
   // wy1 + 5 <= h - 20 of the level) and mask row wy0 - 1 >= 0, all inside the level.
   auto load_row = [&](int r) -> uint32_t {
-    return dev::align_down4(row0 + r * pitch)[lane];
+    // (the empty asm keeps lb's widening to 64 bits next to the load, which then takes the
+    // scalar row address and the 32-bit lb as they are; hoisted out of the band loop, the
+    // widened lb costs a 64-bit vector add per row)
+    uint32_t o = lb;
+    asm volatile("" : "+v"(o));
+    return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(dev::align_down4(row0 + r * pitch)) + o);
   };
   auto fix_row = [&](int r, uint32_t own) -> uint32_t {
     const uint32_t sh = (uint32_t)((uintptr_t)(row0 + r * pitch) & 3);
@@ -205,7 +240,7 @@ __global__ __launch_bounds__(256) void k_fast_rows(FastRowArgs a) {
   // mask bytes of raw row r (all 0xFF without a mask)
   auto load_mrow = [&](int r) -> uint32_t {
     if (!mrow0) return 0xFFFFFFFFu;
-    return reinterpret_cast<const uint32_t*>(mrow0 + r * mpitch)[lane];
+    return *reinterpret_cast<const uint32_t*>(mrow0 + r * mpitch + mlb);
   };
 
   // the score window starts zeroed: rows outside the detection window read as non-corners
@@ -316,7 +351,7 @@ __global__ __launch_bounds__(256) void k_fast_rows(FastRowArgs a) {
                               ((bk(dn) | bk(up)) & (bk(rt) | bk(lf)))) & detm);
     }
     // compaction: the lane's exclusive prefix of its survivor counts (0..4 per row) by DPP
-    // scans, three rows per scan in 10-bit fields (a row's wave total is <= 62 x 4 = 248, so
+    // scans, three rows per scan in 10-bit fields (a row's wave total is < 64 x 4 = 256, so
     // no field carries into the next; one scan per row measured 0.652 against 0.638 ms per
     // step); the four entries per row are written unconditionally, those of non-survivors to a
     // dummy slot
@@ -444,17 +479,18 @@ __global__ __launch_bounds__(256) void k_fast_rows(FastRowArgs a) {
       uint32_t rec = 0;
       if (j < nproc) {
         const int e = list[j], y = e >> 8, x = e & 0xFF;
-        const int cx = xa + x - u.ux0;
+        const bool eb = x >= split4;   // the corner's run, by its column (not by this lane)
+        const int cx = (eb ? cxoB : cxoA) + x;
         k = (int)(((uint32_t)cx * magic) >> 16);
-        const int cs = k * wc, ce = min(cs + wc, span);
+        const int cs = k * wc, ce = min(cs + wc, eb ? spanB : spanA);
+        k += eb ? ncA : 0;
         auto sv = [&](int dy, int dx) -> int { return sc_at(e, dy, dx); };
         const int e0 = sv(0, 0);
         int mx = max(sv(-1, 0), sv(1, 0));
         if (cx > cs) mx = max(mx, fr_max3(sv(-1, -1), sv(0, -1), sv(1, -1)));
         if (cx + 1 < ce) mx = max(mx, fr_max3(sv(-1, 1), sv(0, 1), sv(1, 1)));
         keep = e0 >= 2 && e0 > mx;   // score > 0 and > every in-cell neighbour's score
-        rec = (uint32_t)(xa + x - kMinBorder) | ((uint32_t)(u.wy0 + y - 3 - kMinBorder) << 12) |
-              ((uint32_t)(e0 - 1) << 24);
+        rec = (uint32_t)((eb ? recB : recA) + x + (y << 12)) | ((uint32_t)(e0 - 1) << 24);
       }
       // runByPixelsMask: the mask byte of (y, x) from the lane holding column x of mask row y
       // (row y - (y0 - 1) of the register window m)
@@ -500,7 +536,7 @@ __global__ __launch_bounds__(256) void k_fast_rows(FastRowArgs a) {
     FP_T(t4_);
     FP_ADD(3, t4_ - t3_);
   }
-  if (lane < nc) cnt_out[lane] = cnt;
+  if (lane < nc) cnt_out[cell_l] = cnt;
   zero_count();
   FP_END();
 }
