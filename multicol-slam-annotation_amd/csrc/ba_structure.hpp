@@ -366,7 +366,7 @@ inline void build_structure_fill_par(const mcs_ba_problem& p, bool points_fixed,
 }
 
 // The edge pairs of every lower block in (point, e1, e2) order and the k_schur work items, on
-// the host.  The product builds both on the device (ba.hip, enqueue_pairs); this restatement
+// the host.  The product builds both on the device (ba_pairs.hpp, Optimizer::enqueue_pairs); this restatement
 // is the checker of that build (mcs_ba_check_structure) and the CPU timing reference
 // (tools/bench/structure_bench.cpp).
 inline void build_pairs_host(const mcs_ba_problem& p, HostStruct& s) {

@@ -1,5 +1,5 @@
 // The LM controller of csrc/lm_control.hpp compiled for the host and replayed on scripted
-// trials: the loop of k_lm_replay (csrc/ba.hip), same inputs, same [n][10] output.
+// trials: the loop of k_lm_replay (csrc/ba_kernels.hpp), same inputs, same [n][10] output.
 //   g++ -O2 -std=c++17 -ffp-contract=off -shared -fPIC lm_replay_host.cpp -o liblm_replay_host.so
 #include "../../multicol-slam-annotation_amd/csrc/lm_control.hpp"
 

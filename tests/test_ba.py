@@ -319,6 +319,52 @@ def test_gpu_local_ba_pose_leaves_after_culling(gpu):
     assert np.abs(g["poses"] - h["poses"]).max() < 1e-6
 
 
+def _outlier_points_problem():
+    """_pose_leaves_problem with eight points (three or more edges each, none on the leaving
+    pose) whose every measurement is moved ~2000 px.  Round 1 culls their edges until the point
+    goes bad; an extra observation keeps the point alive one edge longer, so the inlier flags
+    depend on extra_obs, and the points end with at most one edge: not written back."""
+    pr, k = _pose_leaves_problem()
+    n = len(pr["points"])
+    cnt = np.bincount(pr["edge_point"], minlength=n)
+    on_k = np.zeros(n, bool)
+    on_k[pr["edge_point"][pr["edge_pose"] == k]] = True
+    sel = np.isin(pr["edge_point"], np.nonzero((cnt >= 3) & ~on_k)[0][:8])
+    pr["edge_meas"][sel] += np.random.default_rng(1).uniform(-2000.0, 2000.0, (int(sel.sum()), 2))
+    return pr
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", ["pose_leaves", "outlier_points"])
+def test_gpu_local_ba_ex_flows_agree_on_write_back_mask(gpu, which):
+    """local_ba_ex with extra observations on every third point, through the device-culled flow
+    (which falls back to a host round 2 here: a pose leaves), the host-culled flow (timing on) and
+    the oracle: the same point_write mask, inlier flags, write-back and iteration counts.
+
+    On _pose_leaves_problem the oracle writes every point back (point_write is all ones) and
+    its results do not depend on extra_obs, whatever the modulus: point_write cannot, because a
+    point is bad only once fewer than two of its edges are left, which alone clears its flag.
+    The second case adds points that are outliers as a whole: there the oracle's point_write
+    has 10 zeros among 300 and extra_obs changes 4 inlier flags (modulus 3 kept)."""
+    from mcs_amd import ba
+    pr = _pose_leaves_problem()[0] if which == "pose_leaves" else _outlier_points_problem()
+    extra_obs = (np.arange(len(pr["points"])) % 3 == 0).astype(np.int32)
+    o = ob.local_ba_ex(pr, extra_obs)
+    if which == "outlier_points":
+        assert 0 < o["point_write"].sum() < len(o["point_write"])
+        assert not np.array_equal(o["edge_inlier"], ob.local_ba_ex(pr, None)["edge_inlier"])
+    g = ba.Solver().local_ba_ex(pr, extra_obs)
+    H = ba.Solver()
+    H.enable_timing(True)
+    h = H.local_ba_ex(pr, extra_obs)
+    for r in (g, h):
+        assert np.array_equal(r["point_write"], o["point_write"])
+        assert np.array_equal(r["edge_inlier"], o["edge_inlier"])
+        assert r["write_back"] == o["write_back"]
+        assert r["report1"].iterations == o["report1"].iterations
+        assert r["report2"].iterations == o["report2"].iterations
+
+
 @pytest.mark.gpu
 def test_gpu_local_ba_multi_tile_matches_oracle(gpu):
     """LocalBA with 14 local keyframes: 84 pose unknowns, so the reduced system spans two 64x64

@@ -9,7 +9,7 @@ failures in a row, stalls that trip Raul's nBad stop and the terminate action's 
 
 The product's device code is replayed on the same scripted inputs through test hooks that call
 the production device functions (mcs_ba_lm_replay -> lm_start_body / lm_lambda0_body /
-lm_step of csrc/lm_control.hpp, mcs_ba_huber_eval -> huber, csrc/ba.hip) and must reproduce
+lm_step of csrc/lm_control.hpp, mcs_ba_huber_eval -> huber, csrc/ba_edge_math.hpp) and must reproduce
 every lambda, nu and accept / reject decision bit for bit, the number of trials and iterations
 each optimize() call runs, the terminate action's stop flag, and the Huber rho / rho' values.
 The LM controller is plain C++ shared by the device-driven and the host-driven loop; its host
