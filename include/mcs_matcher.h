@@ -708,6 +708,123 @@ int mcs_sim3_solver(int32_t device, const mcs_fuse_targets* kf1, const mcs_sim3_
                     const mcs_sim3_ransac* ransac, const uint8_t* good1, const uint8_t* good2,
                     uint8_t* active1, uint8_t* active2);
 
+/* ---- OptimizeSim3: the Sim3 refinement of a loop candidate ------------------------------------
+ *   int cOptimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12)   src/cOptimizerLoopStuff.cpp:63-270
+ *   VertexSim3Expmap_Multi, EdgeSim3ProjectXYZ_Multi, EdgeInverseSim3ProjectXYZ_Multi
+ *                                                    include/g2o_MultiCol_sim3_expmap.h:117-260
+ *   g2o::Sim3 (exp, map, inverse, operator*)         ThirdParty/g2o/g2o/types/sim3.h:41-292
+ * called per loop candidate by cLoopClosing::ComputeSim3 (src/cLoopClosing.cpp:372-378) after
+ * SearchBySim3.  Here ONE current keyframe KF1 against a batch of T candidates, one workgroup per
+ * candidate, the whole function in one launch: the slot rules (:122-161), both rounds of
+ * Levenberg-Marquardt on the one 7-dof vertex (:209-210, :243-245), the cull between them
+ * (:212-232), the `< 3` return (:240-241), the final flags (:247-263) and the recover (:265-267).
+ * Everything is FP64.  The LM control is g2o's (csrc/lm_control.hpp); the terminate action's stop
+ * flag lives across both rounds, so round 2 runs no iteration after a gain stop in round 1.
+ *
+ * Reproduced as written:
+ *   - e21's information is GetSigma2(octave of keypoint i2), sigma^2 and not 1 / sigma^2 (:194);
+ *   - the observation of e21 is KF2's keypoint i2 = GetIndexInKeyFrame(pKF2)[0], not the matched
+ *     slot (:133, :186);
+ *   - the camera lookup is crossed: e12 projects with camera keypoint_to_cam1[i2] (vPoint2 carries
+ *     SetID(i2), :154), e21 with keypoint_to_cam2[i] (vPoint1 carries SetID(i), :145).  Where that
+ *     lookup leaves the map (i2 >= n1, or i >= n2 of the candidate) the text dereferences end():
+ *     such a slot is dropped, its match set to -1 and it is counted in n_undefined.
+ *     MCS_SIM3OPT_OWN_CAMERA takes keypoint_to_cam1[i] and keypoint_to_cam2[i2] instead;
+ *   - after round 1 a pair is culled when either chi2 is strictly above (1.345 * std_sim)^2;
+ *     with fewer than 3 pairs left the function returns 0 with those matches already nulled and
+ *     the Sim3 unchanged.
+ * The text's edges define no linearizeOplus, so g2o differentiates numerically (delta = 1e-9,
+ * base_binary_edge.hpp:147-172); here the Jacobian is analytic, which agrees with the text to the
+ * scatter of that difference quotient, while every count and flag is exact. */
+#define MCS_SIM3OPT_OWN_CAMERA 1   /* flags: each edge projects with its own observation's camera */
+
+typedef struct mcs_sim3_opt_options {
+  double std_sim;               /* cOptimizer::stdSim: 4.0 (:55); Huber delta = 1.345 * std_sim (:114) */
+  int32_t its_round1;           /* optimize(5) (:210) */
+  int32_t its_clean;            /* nMoreIterations when nBad == 0: 5 (:238) */
+  int32_t its_culled;           /* nMoreIterations when nBad > 0: 10 (:236) */
+  int32_t terminate_max_iter;   /* SparseOptimizerTerminateAction max iterations: 15 (:81) */
+  double gain_threshold;        /* its gain threshold: 1e-6 (:80) */
+  double tau;                   /* LM lambda init factor: 1e-5 (g2o default) */
+  int32_t max_trials;           /* LM maxTrialsAfterFailure: 10 (g2o default) */
+  int32_t flags;                /* MCS_SIM3OPT_* */
+} mcs_sim3_opt_options;
+
+/* The reference's values (:55, :80-81, :210, :234-238 and g2o's defaults), flags = 0. */
+void mcs_sim3_opt_default_options(mcs_sim3_opt_options* o);
+
+/* Outputs of one call, per candidate t; device pointers in the device form, host in the other. */
+typedef struct mcs_sim3_opt_out {
+  int32_t* n_in;               /* [T] the return value (:269); 0 on the `< 3` return (:241) */
+  int32_t* n_corr;             /* [T] nCorrespondences (:163) */
+  int32_t* n_bad;              /* [T] nBad after round 1 (:213-232) */
+  int32_t* n_undefined;        /* [T] slots dropped because the crossed camera lookup leaves its map */
+  double* s12;                 /* [T] the recovered Sim3 (:266-267); the input on the `< 3` return */
+  double* q12;                 /* [T][4] w, x, y, z (Eigen's conversion of the input R on that return) */
+  double* R12;                 /* [T][9] row-major */
+  double* t12;                 /* [T][3] */
+  int32_t* iters;              /* [T][2] iterations run by optimize() in round 1 / round 2 */
+  double* chi2;                /* [T][2] activeRobustChi2 after each round (0 where it did not run) */
+  double* lambda;              /* [T][2] the LM lambda after each round (0 where no iteration ran) */
+  int32_t* trials;             /* nullable [T][2][16] LM trials of every iteration (levenbergIteration()) */
+  double* edge_chi2;           /* nullable [T][n1][2] chi2 of e12 / e21 after the last round run, NaN = slot not kept */
+} mcs_sim3_opt_out;
+
+/* Device scratch of mcs_optimize_sim3_device for <= max_targets candidates and a KF1 of <= max_kp
+ * keypoint slots: the compacted rows of the kept slots. */
+typedef struct mcs_sim3_opt_workspace mcs_sim3_opt_workspace;
+int mcs_sim3_opt_workspace_create(int32_t device, int32_t max_targets, int32_t max_kp,
+                                  mcs_sim3_opt_workspace** out);
+void mcs_sim3_opt_workspace_destroy(mcs_sim3_opt_workspace* ws);
+
+/* OptimizeSim3 (src/cOptimizerLoopStuff.cpp:63-270) for all T candidates in one launch.  The
+ * slot data are those of mcs_sim3_solver_prepare_device:
+ *   d_matches12 [T][n1]   in: KF2 keypoint index whose slot holds pMP2 = vpMatches1[i], -1 = NULL
+ *                         (:124); out: -1 wherever the text nulls the match (:225, :259) and at
+ *                         slots dropped as undefined
+ *   d_ok1 [n1]            KF1's slot i holds a point that is not bad (:135-137)
+ *   d_ok2 [n_kp_total of kf2s]  the matched slot's point is not bad (:137)
+ *   d_first2              i2 = (int)GetIndexInKeyFrame(pKF2)[0] (:133), -1 = does not observe KF2
+ *   d_inv_sigma2_1 [n_levels]   KF1's mvInvLevelSigma2 (:176)
+ *   d_sigma2_2 [n_levels]       KF2's mvLevelSigma2 (:194)
+ *   d_s12 [T], d_R12 [T][9] row-major, d_t12 [T][3]   g2oS12 on entry: Sim3(R, t, s)
+ * Of the sets kp_xy, kp_octave, kp_cam, off, m_t, m_c and cam are read; of the points pos.
+ * A match, first index, octave or camera outside its range drops the slot.  Deterministic: no
+ * floating-point atomics, a reduction order fixed by thread and stride, identical bits from run
+ * to run and for a candidate alone or in a batch.  Stream-ordered, no host synchronisation, no
+ * allocation with a workspace; ws NULL = a temporary one is allocated and freed (which
+ * synchronises).  MCS_ERR_ARG: kf1->n_targets != 1, T or n1 above the workspace, more than 8
+ * cameras, a KF1 of 2^19 keypoints or more, n_cams / n_levels differing between kf1 and kf2s,
+ * points not matching their set, iteration counts outside [0, 16], max_trials outside [1, 64],
+ * std_sim not positive, an unknown flag, a null buffer. */
+int mcs_optimize_sim3_device(mcs_sim3_opt_workspace* ws, const mcs_fuse_targets* kf1,
+                             const mcs_sim3_points* pts1, const mcs_fuse_targets* kf2s,
+                             const mcs_sim3_points* pts2, int32_t* d_matches12, const uint8_t* d_ok1,
+                             const uint8_t* d_ok2, const int32_t* d_first2,
+                             const double* d_inv_sigma2_1, const double* d_sigma2_2,
+                             const double* d_s12, const double* d_R12, const double* d_t12,
+                             const mcs_sim3_opt_options* opts, const mcs_sim3_opt_out* out,
+                             void* stream);
+
+/* vpMapPointMatches as ComputeSim3 hands it to OptimizeSim3 (src/cLoopClosing.cpp:354-369), one
+ * launch: d_matches12[t][i] = d_bow12[t][i] where d_inlier[t][i] (the RANSAC inliers' BoW
+ * matches, :354-360), else d_new12[t][i] when >= 0 (SearchBySim3 fills the empty entries, :369),
+ * else -1.  All [T][n1].  MCS_ERR_ARG: negative counts, T * n1 >= 2^31, a null buffer. */
+int mcs_sim3_merge_matches_device(const int32_t* d_bow12, const uint8_t* d_inlier,
+                                  const int32_t* d_new12, int32_t T, int32_t n1,
+                                  int32_t* d_matches12, void* stream);
+
+/* Host-buffer form for the call site (src/cLoopClosing.cpp:372): uploads, runs
+ * mcs_optimize_sim3_device on `device`, downloads; matches12 is in-out, the pointers of `out` are
+ * host outputs, each nullable.  Also MCS_ERR_ARG for malformed offsets; all argument errors are
+ * returned before any device use.  MCS_ERR_NO_DEVICE without a GPU. */
+int mcs_optimize_sim3(int32_t device, const mcs_fuse_targets* kf1, const mcs_sim3_points* pts1,
+                      const mcs_fuse_targets* kf2s, const mcs_sim3_points* pts2, int32_t* matches12,
+                      const uint8_t* ok1, const uint8_t* ok2, const int32_t* first2,
+                      const double* inv_sigma2_1, const double* sigma2_2, const double* s12,
+                      const double* R12, const double* t12, const mcs_sim3_opt_options* opts,
+                      const mcs_sim3_opt_out* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -739,6 +739,56 @@ class Sim3Solver {
   double s_ = 0, R_[9] = {0}, t_[3] = {0}, T_[16] = {0};
 };
 
+// cOptimizer::OptimizeSim3 (src/cOptimizerLoopStuff.cpp:63-270) at cLoopClosing::ComputeSim3
+// (src/cLoopClosing.cpp:372): int OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12), on
+// mcs_optimize_sim3.  vpMatches1 [n1] (in / out): the matched point as a keypoint of kf2 (its
+// slot's map point), -1 = NULL; entries the text nulls come back as -1.  first2 [n2]:
+// (int)GetIndexInKeyFrame(pKF2)[0] of the slot's point.  inv_sigma2_1 / sigma2_2: KF1's
+// mvInvLevelSigma2 and KF2's mvLevelSigma2 (the text weights e21 with sigma^2, :194).
+// g2oS12 (in / out) is left as it was when fewer than 3 pairs survive round 1 (:240-241).
+// Returns nIn.  options NULL = the reference's values; its flags select MCS_SIM3OPT_OWN_CAMERA.
+struct Sim3Transform {              // g2o::Sim3(R, t, s)
+  double s = 1.0, R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
+};
+inline int OptimizeSim3(const FuseRig& rig, const Sim3KeyFrame& kf1, const Sim3KeyFrame& kf2,
+                        std::vector<int32_t>& vpMatches1, const std::vector<int32_t>& first2,
+                        const std::vector<double>& inv_sigma2_1, const std::vector<double>& sigma2_2,
+                        Sim3Transform& g2oS12, const mcs_sim3_opt_options* options = nullptr, int device = 0) {
+  if (!kf1.kf || !kf2.kf) throw std::invalid_argument("OptimizeSim3: a keyframe is missing");
+  const int n1 = (int)kf1.kf->kp_octave.size(), n2 = (int)kf2.kf->kp_octave.size();
+  const int32_t L = (int32_t)rig.scale.size(), C = rig.n_cams, one[2] = {0, n1}, two[2] = {0, n2};
+  if ((int)vpMatches1.size() != n1 || (int)first2.size() != n2 || (int)kf1.has_mp.size() != n1 ||
+      (int)kf1.bad.size() != n1 || (int)kf2.bad.size() != n2 || (int)inv_sigma2_1.size() != L ||
+      (int)sigma2_2.size() != L || (int)kf1.pos.size() != 3 * n1 || (int)kf2.pos.size() != 3 * n2)
+    throw std::invalid_argument("OptimizeSim3: matches / first2 / bad / pos / sigma2 do not fit the keyframes");
+  std::vector<uint8_t> ok1((size_t)n1 + 1), ok2((size_t)n2 + 1);
+  for (int i = 0; i < n1; i++) ok1[i] = kf1.has_mp[i] && !kf1.bad[i];    // pMP1 && !pMP1->isBad() (:135-137)
+  for (int i = 0; i < n2; i++) ok2[i] = !kf2.bad[i];                      // !pMP2->isBad() (:137)
+  const FuseKeyFrame &a = *kf1.kf, &b = *kf2.kf;
+  mcs_fuse_targets s1{1, n1, C, 32, L, rig.mirror_w, rig.mirror_h, one, a.kp_xy.data(), a.kp_octave.data(),
+                      a.kp_cam.data(), nullptr, nullptr, nullptr, a.m_t, rig.m_c.data(), rig.cam.data(), nullptr,
+                      nullptr, nullptr, nullptr, nullptr};
+  mcs_fuse_targets s2{1, n2, C, 32, L, rig.mirror_w, rig.mirror_h, two, b.kp_xy.data(), b.kp_octave.data(),
+                      b.kp_cam.data(), nullptr, nullptr, nullptr, b.m_t, rig.m_c.data(), rig.cam.data(), nullptr,
+                      nullptr, nullptr, nullptr, nullptr};
+  mcs_sim3_points p1{n1, kf1.pos.data(), nullptr, nullptr, nullptr}, p2{n2, kf2.pos.data(), nullptr, nullptr, nullptr};
+  mcs_sim3_opt_options o;
+  if (options) o = *options; else mcs_sim3_opt_default_options(&o);
+  int32_t n_in = 0, n_corr = 0, n_bad = 0, n_undef = 0, iters[2];
+  double s = 0, q[4], R[9], t[3], chi2[2], lambda[2];
+  mcs_sim3_opt_out out{&n_in, &n_corr, &n_bad, &n_undef, &s, q, R, t, iters, chi2, lambda, nullptr, nullptr};
+  std::vector<int32_t> m12(vpMatches1);
+  m12.push_back(-1);
+  check(mcs_optimize_sim3(device, &s1, &p1, &s2, &p2, m12.data(), ok1.data(), ok2.data(), first2.data(),
+                          inv_sigma2_1.data(), sigma2_2.data(), &g2oS12.s, g2oS12.R, g2oS12.t, &o, &out),
+        "mcs_optimize_sim3");
+  std::copy(m12.begin(), m12.begin() + n1, vpMatches1.begin());
+  g2oS12.s = s;
+  std::memcpy(g2oS12.R, R, sizeof(R));
+  std::memcpy(g2oS12.t, t, sizeof(t));
+  return n_in;
+}
+
 // cLocalMapping::CreateNewMapPoints (src/cLocalMapping.cpp:224-386) at its call site (:99): the
 // neighbour loop (SearchForTriangulationRaw, then the per-match loop :272-382) in one device call
 // (mcs_create_new_map_points).  The caller does what needs the map: the neighbours

@@ -185,6 +185,13 @@ SIGNATURES = {
     "mcs_sim3_solver_iterate_device": (ctypes.c_int, [_P, _P, _P, _I32, ctypes.c_double, _I32, _I32, _I32, _P, _P]),
     "mcs_sim3_solver_active_device": (ctypes.c_int, [_P] * 10),
     "mcs_sim3_solver": (ctypes.c_int, [_I32] + [_P] * 11 + [_I32, ctypes.c_double, _I32, _I32, _I32] + [_P] * 6),
+    # OptimizeSim3 (include/mcs_matcher.h; wrappers in mcs_amd/sim3_opt.py)
+    "mcs_sim3_opt_default_options": (None, [_P]),
+    "mcs_sim3_opt_workspace_create": (ctypes.c_int, [_I32, _I32, _I32, _P]),
+    "mcs_sim3_opt_workspace_destroy": (None, [_P]),
+    "mcs_optimize_sim3_device": (ctypes.c_int, [_P] * 17),
+    "mcs_sim3_merge_matches_device": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _P, _P]),
+    "mcs_optimize_sim3": (ctypes.c_int, [_I32] + [_P] * 15),
     # CreateNewMapPoints (include/mcs_newpoints.h; wrappers in mcs_amd/new_points.py)
     "mcs_newpts_workspace_create": (ctypes.c_int, [_I32, _I32, _P]),
     "mcs_newpts_workspace_destroy": (None, [_P]),

@@ -1,0 +1,131 @@
+"""Writes tests/golden/sim3opt_ref.npz: cOptimizer::OptimizeSim3 (reference
+src/cOptimizerLoopStuff.cpp:63-270) run by the reference's own g2o on the cases of
+tests/sim3opt_cases.py.
+
+tests/cpp/sim3opt_g2o_driver.cpp (our restatement of the function body) is compiled into a
+temporary directory against the reference checkout's g2o / Eigen headers and linked with
+oracle/_ref/libg2o_ref.so and oracle/build/liboracle.so, both made by __graft_entry__.build().
+Every case runs three times: g2o's own numeric Jacobian (delta = 1e-9), and the same central
+scheme at 0.5e-9 and 2e-9.  The fixture holds numbers only: per case the SHA-256 of the seeded
+inputs, the outputs of the delta = 1e-9 run and, per real field, the largest pairwise difference
+between the three runs (`measured_<case>_<field>`), from which the tests derive their tolerance.
+
+Conditions checked here, on the reference runs alone (a case that breaks one needs another seed):
+the three runs share iteration counts, trial counts and every integer output; no edge of either
+round has a chi2 within 1e-3 relative of deltaHuber2.  g2o does not expose rho of a trial; that no
+decision is marginal is covered by the three runs taking the same trial sequences.
+
+    python tests/golden/gen_sim3opt_ref.py          # needs the reference checkout
+"""
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+for p in (ROOT, os.path.join(ROOT, "multicol-slam-annotation_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+from tests import sim3opt_cases as sc  # noqa: E402
+
+OUT = os.path.join(HERE, "sim3opt_ref.npz")
+REF = os.environ.get("MCS_REFERENCE", "/root/reference")
+REALS = ("s", "q", "t", "chi2", "edge_chi2")
+INTS = ("n_in", "n_corr", "n_bad", "iters", "trials", "matches12")
+DELTA2 = (1.345 * 4.0) ** 2
+
+
+def build_driver(tmp):
+    ref = os.path.join(ROOT, "oracle", "_ref")
+    exe = os.path.join(tmp, "sim3opt_g2o_driver")
+    g2o = os.path.join(REF, "ThirdParty", "g2o")
+    cmd = ["g++", "-std=gnu++14", "-O2", "-ffp-contract=off", "-fno-fast-math", "-DNDEBUG", "-w",
+           "-I", os.path.join(ref, "include"), "-I", os.path.join(ref, "include", "a", "b"), "-I", g2o,
+           "-I", os.path.join(REF, "ThirdParty", "Eigen"),
+           os.path.join(ROOT, "tests", "cpp", "sim3opt_g2o_driver.cpp"), "-o", exe,
+           "-L", ref, "-lg2o_ref", "-L", os.path.join(ROOT, "oracle", "build"), "-loracle",
+           "-Wl,-rpath," + ref, "-Wl,-rpath," + os.path.join(ROOT, "oracle", "build")]
+    subprocess.check_call(cmd)
+    return exe
+
+
+def qdiff(a, b):
+    return min(np.abs(a - b).max(), np.abs(a + b).max())
+
+
+def diff(field, a, b):
+    if field == "q":
+        return qdiff(a, b)
+    a, b = np.asarray(a, np.float64).reshape(-1), np.asarray(b, np.float64).reshape(-1)
+    ok = ~(np.isnan(a) & np.isnan(b))
+    return float(np.abs(a[ok] - b[ok]).max()) if ok.any() else 0.0
+
+
+def run_reference(exe, case, tmp):
+    """The three runs of one case -> [mode][candidate] dicts."""
+    path = os.path.join(tmp, case["name"] + ".txt")
+    sc.write_case_file(case, path, matches12=sc.without_undefined(case))
+    n1 = case["matches12"].shape[1]
+    return [sc.parse_results(subprocess.check_output([exe, path, str(mode)], text=True), n1) for mode in range(3)]
+
+
+def check_and_measure(name, runs):
+    T = len(runs[0])
+    spread = {f: np.zeros(T) for f in REALS}
+    for t in range(T):
+        for f in INTS:
+            for r in runs[1:]:
+                assert np.array_equal(runs[0][t][f], r[t][f]), "%s[%d]: %s differs between the deltas" % (name, t, f)
+        for r in runs:
+            for key in ("edge_chi2", "edge_chi2_r1"):
+                e = r[t].get(key)
+                if e is None:
+                    continue
+                e = e[~np.isnan(e)]
+                assert not np.any(np.abs(e - DELTA2) < 1e-3 * DELTA2), "%s[%d]: a chi2 sits on deltaHuber2" % (name, t)
+        for f in REALS:
+            for a in range(3):
+                for b in range(a + 1, 3):
+                    spread[f][t] = max(spread[f][t], diff(f, runs[a][t][f], runs[b][t][f]))
+    return spread
+
+
+def generate():
+    data = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = build_driver(tmp)
+        results = {}
+        for name in sc.CASES:
+            case = sc.make_case(name)
+            runs = run_reference(exe, case, tmp)
+            spread = check_and_measure(name, runs)
+            results[name] = runs[0]
+            data[name + "_sha256"] = np.array(sc.digest(case))
+            for f in INTS + REALS + ("lambda",):
+                data["%s_%s" % (name, f)] = np.stack([np.asarray(r[f]) for r in runs[0]])
+            data[name + "_n_undefined"] = np.array([len(u) for u in case["undefined"]], np.int32)
+            for f in REALS:
+                data["measured_%s_%s" % (name, f)] = spread[f]
+            print(name, "n_corr", data[name + "_n_corr"], "n_bad", data[name + "_n_bad"], "n_in", data[name + "_n_in"],
+                  "iters", data[name + "_iters"].tolist(), "trials", [r["trials"].sum(1).tolist() for r in runs[0]])
+            print("spread", {f: float(spread[f].max()) for f in REALS})
+    # what the table of cases promises, on the reference runs
+    assert (data["A_clean_n_bad"] == 0).all()
+    assert (data["B_outliers_n_bad"] > 0).all()
+    assert (data["D_below3_n_in"] == 0).all() and data["D_below3_iters"][0, 1] == 0
+    assert data["F_gainstop_iters"][0, 1] == 0, "F_gainstop: the reference's round 2 must run no iteration"
+    assert (data["C_batch_n_corr"] == [0, 2, 3, 70]).all()
+    assert data["I_round2_iters"][0, 1] > 0, "I_round2: the reference's round 2 must iterate"
+    b, g = results["B_outliers"][0], results["G_own_camera"][0]
+    tol = max(8 * data["measured_B_outliers_s"].max(), 1e-9)
+    assert abs(b["s"] - g["s"]) > tol or b["n_in"] != g["n_in"], "G_own_camera must differ from B_outliers"
+    np.savez_compressed(OUT, **data)
+    print("wrote", OUT, os.path.getsize(OUT), "bytes")
+
+
+if __name__ == "__main__":
+    generate()
