@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "../../include/mcs_ba.h"
+#include "../../include/mcs_essgraph.h"
 #include "../../include/mcs_extractor.h"
 #include "../../include/mcs_kfdb.h"
 #include "../../include/mcs_matcher.h"
@@ -787,6 +788,113 @@ inline int OptimizeSim3(const FuseRig& rig, const Sim3KeyFrame& kf1, const Sim3K
   std::memcpy(g2oS12.R, R, sizeof(R));
   std::memcpy(g2oS12.t, t, sizeof(t));
   return n_in;
+}
+
+// cOptimizer::OptimizeEssentialGraph (src/cOptimizerLoopStuff.cpp:273-519) at cLoopClosing::CorrectLoop
+// (src/cLoopClosing.cpp:648): void OptimizeEssentialGraph(pMap, pLoopMKF, pCurMKF, Scurw,
+// NonCorrectedSim3, CorrectedSim3, LoopConnections), on mcs_essgraph_select_edges and
+// mcs_optimize_essential_graph over the flat map.  Keyframes in ascending mnId, none bad.
+struct EssentialGraphKeyFrame {
+  int64_t id = 0;                        // mnId
+  double pose_inv[16] = {0};             // in: GetPoseInverse(), row-major (read when !has_corrected, :331-336)
+  double pose[16] = {0};                 // out: the SetPose argument (:490)
+  int32_t parent = -1;                   // GetParent() as an index into the keyframe list
+  bool has_corrected = false;            // key of CorrectedSim3 / NonCorrectedSim3
+  double corrected[8] = {1, 1, 0, 0, 0, 0, 0, 0};      // CorrectedSim3[kf] as s, qw qx qy qz, tx ty tz
+  double non_corrected[8] = {1, 1, 0, 0, 0, 0, 0, 0};  // NonCorrectedSim3[kf]
+  std::vector<int32_t> loop_edges;       // GetLoopEdges() as indices
+  std::vector<int32_t> covisibles, cov_weights;         // GetCovisiblesByWeight(0) order with GetWeight
+  std::vector<int32_t> loop_connections, lc_weights;    // LoopConnections[kf] with GetWeight
+};
+struct EssentialGraphPoints {            // GetAllMapPoints()
+  std::vector<double> pos;               // [P][3] GetWorldPos(), corrected in place
+  std::vector<int64_t> corrected_by, corrected_ref, ref_kf;   // mnCorrectedByKF, mnCorrectedReference, reference mnId
+  std::vector<uint8_t> bad;
+};
+struct EssentialGraphReport { int32_t iterations = 0, n_edges = 0, counts[4] = {0, 0, 0, 0}; double chi2 = 0, lambda = 0; };
+
+inline EssentialGraphReport OptimizeEssentialGraph(std::vector<EssentialGraphKeyFrame>& kfs, EssentialGraphPoints& pts,
+                                                   int loop_index, int cur_index,
+                                                   const mcs_essgraph_options* options = nullptr, int device = 0) {
+  const int N = (int)kfs.size(), P = (int)pts.bad.size();
+  if (N < 1 || loop_index < 0 || loop_index >= N || cur_index < 0 || cur_index >= N)
+    throw std::invalid_argument("OptimizeEssentialGraph: loop / current keyframe outside the list");
+  if ((int)pts.pos.size() != 3 * P || (int)pts.corrected_by.size() != P || (int)pts.corrected_ref.size() != P ||
+      (int)pts.ref_kf.size() != P)
+    throw std::invalid_argument("OptimizeEssentialGraph: the point arrays do not agree in length");
+  std::vector<int64_t> ids(N);
+  std::vector<int32_t> parent(N), lp(1, 0), li, cp(1, 0), ci, cw, kp(1, 0), ki, kw;
+  std::vector<uint8_t> hc(N);
+  std::vector<double> Scw(8 * (size_t)N), Snc(8 * (size_t)N);
+  std::unordered_map<int64_t, int32_t> index_of;
+  for (int i = 0; i < N; i++) {
+    const EssentialGraphKeyFrame& k = kfs[i];
+    if (k.covisibles.size() != k.cov_weights.size() || k.loop_connections.size() != k.lc_weights.size())
+      throw std::invalid_argument("OptimizeEssentialGraph: neighbours and weights do not agree in length");
+    ids[i] = k.id; parent[i] = k.parent; hc[i] = k.has_corrected;
+    index_of[k.id] = i;
+    li.insert(li.end(), k.loop_edges.begin(), k.loop_edges.end()); lp.push_back((int32_t)li.size());
+    ci.insert(ci.end(), k.covisibles.begin(), k.covisibles.end());
+    cw.insert(cw.end(), k.cov_weights.begin(), k.cov_weights.end()); cp.push_back((int32_t)ci.size());
+    ki.insert(ki.end(), k.loop_connections.begin(), k.loop_connections.end());
+    kw.insert(kw.end(), k.lc_weights.begin(), k.lc_weights.end()); kp.push_back((int32_t)ki.size());
+    double* S = &Scw[8 * (size_t)i];
+    if (k.has_corrected) {
+      std::memcpy(S, k.corrected, sizeof(k.corrected));
+      std::memcpy(&Snc[8 * (size_t)i], k.non_corrected, sizeof(k.non_corrected));
+    } else {
+      // g2o::Sim3(R, t, 1.0) of GetPoseInverse() (:331-336): Eigen's Quaterniond(Matrix3d)
+      const double* M = k.pose_inv;
+      const double m[9] = {M[0], M[1], M[2], M[4], M[5], M[6], M[8], M[9], M[10]};
+      double q[4], t = m[0] + m[4] + m[8];
+      if (t > 0.0) {
+        t = std::sqrt(t + 1.0); q[0] = 0.5 * t; t = 0.5 / t;
+        q[1] = (m[7] - m[5]) * t; q[2] = (m[2] - m[6]) * t; q[3] = (m[3] - m[1]) * t;
+      } else {
+        int a = 0;
+        if (m[4] > m[0]) a = 1;
+        if (m[8] > m[4 * a]) a = 2;
+        const int b = (a + 1) % 3, c = (b + 1) % 3;
+        t = std::sqrt(m[4 * a] - m[4 * b] - m[4 * c] + 1.0); q[1 + a] = 0.5 * t; t = 0.5 / t;
+        q[0] = (m[3 * c + b] - m[3 * b + c]) * t;
+        q[1 + b] = (m[3 * b + a] + m[3 * a + b]) * t; q[1 + c] = (m[3 * c + a] + m[3 * a + c]) * t;
+      }
+      S[0] = 1.0; S[1] = q[0]; S[2] = q[1]; S[3] = q[2]; S[4] = q[3]; S[5] = M[3]; S[6] = M[7]; S[7] = M[11];
+      std::memcpy(&Snc[8 * (size_t)i], S, 8 * sizeof(double));
+    }
+  }
+  mcs_essgraph_map m{N, ids.data(), parent.data(), hc.data(), lp.data(), li.data(), cp.data(), ci.data(), cw.data(),
+                     kp.data(), ki.data(), kw.data(), cur_index, loop_index, 100};
+  EssentialGraphReport rep;
+  int32_t E = 0;
+  int rc = mcs_essgraph_select_edges(&m, nullptr, 0, &E, rep.counts);
+  if (rc != MCS_OK && rc != MCS_ERR_CAPACITY) check(rc, "mcs_essgraph_select_edges");
+  std::vector<int32_t> edges(3 * (size_t)E + 3);
+  check(mcs_essgraph_select_edges(&m, edges.data(), E, &E, rep.counts), "mcs_essgraph_select_edges");
+  rep.n_edges = E;
+  std::vector<int32_t> ref(P + 1);
+  for (int j = 0; j < P; j++) {          // :501-507
+    const int64_t id = pts.corrected_by[j] == kfs[cur_index].id ? pts.corrected_ref[j] : pts.ref_kf[j];
+    auto it = index_of.find(id);
+    if (it == index_of.end() && !pts.bad[j]) throw std::invalid_argument("OptimizeEssentialGraph: a point names no keyframe");
+    ref[j] = it == index_of.end() ? 0 : it->second;
+  }
+  mcs_essgraph_options o;
+  if (options) o = *options; else mcs_essgraph_default_options(&o);
+  if (o.tile_band == 0) o.tile_band = mcs_essgraph_tile_band(N, loop_index, edges.data(), E);
+  std::vector<double> pose(16 * (size_t)N), chi2(MCS_ESSGRAPH_MAX_ITERATIONS);
+  int32_t status = 0;
+  mcs_essgraph_out out{nullptr, nullptr, pose.data(), &rep.iterations, nullptr, chi2.data(), &rep.lambda, nullptr, &status};
+  pts.pos.resize(3 * (size_t)P + 3);
+  pts.bad.resize((size_t)P + 1);
+  rc = mcs_optimize_essential_graph(device, N, Scw.data(), Snc.data(), loop_index, E, edges.data(), P, pts.pos.data(),
+                                    ref.data(), pts.bad.data(), &o, &out);
+  pts.pos.resize(3 * (size_t)P);
+  pts.bad.resize((size_t)P);
+  check(rc, "mcs_optimize_essential_graph");
+  for (int i = 0; i < N; i++) std::memcpy(kfs[i].pose, &pose[16 * (size_t)i], 16 * sizeof(double));
+  rep.chi2 = rep.iterations > 0 ? chi2[rep.iterations - 1] : 0.0;
+  return rep;
 }
 
 // cLocalMapping::CreateNewMapPoints (src/cLocalMapping.cpp:224-386) at its call site (:99): the

@@ -192,6 +192,17 @@ SIGNATURES = {
     "mcs_optimize_sim3_device": (ctypes.c_int, [_P] * 17),
     "mcs_sim3_merge_matches_device": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _P, _P]),
     "mcs_optimize_sim3": (ctypes.c_int, [_I32] + [_P] * 15),
+    # OptimizeEssentialGraph (include/mcs_essgraph.h; wrappers in mcs_amd/essential_graph.py)
+    "mcs_essgraph_select_edges": (ctypes.c_int, [_P, _P, _I32, _P, _P]),
+    "mcs_essgraph_default_options": (None, [_P]),
+    "mcs_essgraph_tile_band": (_I32, [_I32, _I32, _P, _I32]),
+    "mcs_essgraph_supported": (ctypes.c_int, [_I32, _I32]),
+    "mcs_essgraph_workspace_create": (ctypes.c_int, [_I32, _I32, _I32, _I32, _P]),
+    "mcs_essgraph_workspace_destroy": (None, [_P]),
+    "mcs_essgraph_resolve_point_refs_device": (ctypes.c_int, [_I32, _P, _I32, _P, _P, _P, _I64, _P, _P]),
+    "mcs_optimize_essential_graph_device": (ctypes.c_int, [_P, _I32, _P, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P,
+                                                            _P]),
+    "mcs_optimize_essential_graph": (ctypes.c_int, [_I32, _I32, _P, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P]),
     # CreateNewMapPoints (include/mcs_newpoints.h; wrappers in mcs_amd/new_points.py)
     "mcs_newpts_workspace_create": (ctypes.c_int, [_I32, _I32, _P]),
     "mcs_newpts_workspace_destroy": (None, [_P]),
