@@ -15,6 +15,8 @@ FLOOR = 1e-9
 REALS = ("sim3", "pose", "points", "chi2", "edge_chi2")
 INTS = ("edges", "counts", "iterations", "trials")
 
+ONE_TRIAL = dict(iterations=1, max_trials=1, lambda0=1e-2)
+
 # drift = (rotation rad, translation, scale) accumulated over the whole chain
 CASES = {
     "A_ring6": dict(seed=111, N=6, drift=(0.05, 0.15, 1.05), P=12),
@@ -23,6 +25,18 @@ CASES = {
     "D_gaps": dict(seed=114, N=15, drift=(0.06, 0.2, 1.06), P=12, gaps=True, loop=7),
     "E_consistent": dict(seed=15, N=10, drift=None, P=12),
     "F_large": dict(seed=16, N=12, drift=(0.3, 0.4, 1.3), P=12),
+    # One trial at a moderate first damping: one linearisation, assembly, solve, update and chi2 at
+    # sizes past one round of every kernel (a full run is not reproducible there).
+    # G: the loop keyframe in a middle tile, 11 tiles of band 2, three chi2 partials; H: the content
+    # of C_cov40 at 15 tiles with a wide band; J: more than 256 keyframes and points, 33 tiles;
+    # I: more than 16384 edges (the stride loop of k_chi2, all 64 partials), band 8 of 33 tiles.
+    # One damped step reaches the keyframes next to the fixed one, and those before it, only
+    # through neighbours several keyframes apart: with nbr below 6 (G) and 30 (J) fewer than 90 %
+    # of the keyframes move by 100 tolerances, which the generator demands
+    "G_mid100": dict(seed=201, N=100, drift=(0.10, 0.5, 1.10), P=12, nbr=6, loop=37, opts=ONE_TRIAL),
+    "H_cov130": dict(seed=224, N=130, drift=(0.10, 0.5, 1.10), P=200, cov=True, n_corr=4, nbr=4, opts=ONE_TRIAL),
+    "J_n300": dict(seed=252, N=300, drift=(0.10, 0.5, 1.10), P=600, nbr=30, opts=ONE_TRIAL),
+    "I_dense300": dict(seed=242, N=300, drift=(0.05, 0.25, 1.05), P=12, nbr=62, opts=ONE_TRIAL),
 }
 
 
@@ -157,7 +171,7 @@ def make_case(name, seed=None):
                 cov_ptr=cp, cov_idx=np.array([c for c, _ in cf], np.int32), cov_w=np.array([w for _, w in cf], np.int32),
                 lc_ptr=lcp, lc_idx=np.array([c for c, _ in lcf], np.int32), lc_w=np.array([w for _, w in lcf], np.int32),
                 pos=pos, corrected_by=corrected_by, corrected_ref=corrected_ref, ref_kf=ids[ref], bad=bad,
-                opts=default_options())
+                opts=dict(default_options(), **P.get("opts", {})))
 
 
 def default_options():

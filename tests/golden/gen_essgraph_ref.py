@@ -13,7 +13,13 @@ Sim3(update) of the list of essgraph_cases.log_exp_inputs.
 
 Conditions checked here, on the reference runs alone (a case that breaks one needs another seed):
 the three runs share every integer output; at no linearisation point is any edge's |sigma| or
-1 - d within 10 % of 1e-5.
+1 - d within 10 % of 1e-5.  The one-trial cases (essgraph_cases.ONE_TRIAL) also need the trial
+accepted in all three runs and at least 90 % of the free keyframes moved by more than 100 x the
+case's `sim3` tolerance, so that a wrong solve cannot hide in a step that did nothing.
+
+For the one-trial cases the host replica (tests/cpp/essgraph_host.cpp) runs too, at the steps 5e-9,
+1e-8 and 2e-8: its 1e-8 outputs are stored as `host_<case>_<field>` and their spread as
+`measured_host_<case>_<field>`, the tighter second tier of tests/test_essgraph_gpu.py.
 
     python tests/golden/gen_essgraph_ref.py          # needs the reference checkout
 """
@@ -55,22 +61,60 @@ def run_reference(exe, case, tmp, modes=(0, 1, 2)):
     return [ec.parse_results(subprocess.check_output([exe, path, str(mode)], text=True)) for mode in modes]
 
 
+def build_host(tmp):
+    exe = os.path.join(tmp, "essgraph_host")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror",
+                           os.path.join(ROOT, "tests", "cpp", "essgraph_host.cpp"), "-o", exe])
+    return exe
+
+
+HOST_STEPS = ("1e-8", "5e-9", "2e-8")
+
+
+def run_host(host, case, tmp):
+    """The host replica at its own step and at half and twice that; the case file is the one
+    run_reference wrote."""
+    path = os.path.join(tmp, case["name"] + ".txt")
+    ec.write_case_file(case, path)
+    return [ec.parse_results(subprocess.check_output([host, "run", path, d], text=True)) for d in HOST_STEPS]
+
+
+def spread_of(runs):
+    return {f: max(ec.diff(f, runs[a][f], runs[b][f]) for a in range(3) for b in range(a + 1, 3)) for f in ec.REALS}
+
+
+def one_trial(case):
+    o = case["opts"]
+    return o["iterations"] == 1 and o["max_trials"] == 1
+
+
+def check_one_trial(name, case, runs, spread):
+    """The conditions of a one-trial case on the reference runs -> the fraction of free keyframes moved."""
+    for r in runs:
+        assert r["iterations"] == 1 and r["trials"].tolist() == [1], "%s: not one trial" % name
+        assert r["chi2"][0] < r["chi2_initial"], "%s: the trial was rejected" % name
+    want = runs[0]["sim3"]
+    tol = max(8.0 * spread["sim3"], ec.FLOOR * float(np.abs(want).max()))
+    free = np.arange(case["N"]) != case["loop"]
+    move = np.array([ec.sim3_diff(want[i], case["Scw"][i]) for i in range(case["N"])])
+    frac = float((move[free] > 100.0 * tol).mean())
+    assert frac >= 0.9, "%s: only %.3f of the free keyframes move by 100 x the sim3 tolerance" % (name, frac)
+    return frac
+
+
 def check_and_measure(name, runs):
     for f in ec.INTS:
         for r in runs[1:]:
             assert np.array_equal(runs[0][f], r[f]), "%s: %s differs between the deltas" % (name, f)
     for r in runs:
         assert r["branch_margin"] > 0.1, "%s: an edge sits within 10 %% of a 1e-5 branch threshold" % name
-    spread = {}
-    for f in ec.REALS:
-        spread[f] = max(ec.diff(f, runs[a][f], runs[b][f]) for a in range(3) for b in range(a + 1, 3))
-    return spread
+    return spread_of(runs)
 
 
 def generate():
     data = {}
     with tempfile.TemporaryDirectory() as tmp:
-        exe = build_driver(tmp)
+        exe, host = build_driver(tmp), build_host(tmp)
         for name in ec.CASES:
             case = ec.make_case(name)
             runs = run_reference(exe, case, tmp)
@@ -87,6 +131,19 @@ def generate():
                   (runs[0]["chi2_initial"], runs[0]["chi2"][-1] if len(runs[0]["chi2"]) else 0.0),
                   "margin %.3g" % min(r["branch_margin"] for r in runs))
             print("  spread", {f: float(spread[f]) for f in ec.REALS})
+            if one_trial(case):
+                frac = check_one_trial(name, case, runs, spread)
+                hruns = run_host(host, case, tmp)
+                for f in ("edges", "counts", "iterations", "trials"):
+                    for r in hruns:
+                        assert np.array_equal(r[f], runs[0][f]), "%s: %s of the host replica differs" % (name, f)
+                hspread = spread_of(hruns)
+                for f in ("iterations", "trials") + ec.REALS:
+                    data["host_%s_%s" % (name, f)] = np.asarray(hruns[0][f])
+                for f in ec.REALS:
+                    data["measured_host_%s_%s" % (name, f)] = np.float64(hspread[f])
+                print("  moved %.3f of the free keyframes; host spread" % frac, {f: float(hspread[f]) for f in ec.REALS})
+                print("  host - g2o", {f: ec.diff(f, hruns[0][f], runs[0][f]) for f in ec.REALS})
         logs, exps = ec.log_exp_inputs()
         path = os.path.join(tmp, "list.txt")
         ec.write_list_file(path, logs, exps)
@@ -99,6 +156,13 @@ def generate():
     assert data["A_ring6_counts"].tolist() == [1, 5, 0, 5]
     c = data["C_cov40_counts"].tolist()
     assert c[0] == 4 and c[1] == 39 and c[2] == 1, c
+    T = lambda n: (7 * (ec.CASES[n]["N"] - 1) + 63) // 64  # noqa: E731  (tiles of 64 rows, 7 per free keyframe)
+    assert [T(n) for n in ("G_mid100", "H_cov130", "J_n300", "I_dense300")] == [11, 15, 33, 33]
+    assert 7 * ec.CASES["G_mid100"]["loop"] // 64 not in (0, T("G_mid100") - 1), "G_mid100: the loop keyframe in a middle tile"
+    assert len(data["G_mid100_edges"]) > 256 and len(data["I_dense300_edges"]) > 16384
+    c = data["H_cov130_counts"].tolist()
+    assert c[0] == 4 and c[1] == 129 and c[2] == 1, c
+    assert ec.CASES["J_n300"]["N"] > 256 and ec.CASES["J_n300"]["P"] > 256
     np.savez_compressed(OUT, **data)
     print("wrote", OUT, os.path.getsize(OUT), "bytes")
 

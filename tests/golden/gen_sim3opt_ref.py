@@ -123,6 +123,10 @@ def generate():
     b, g = results["B_outliers"][0], results["G_own_camera"][0]
     tol = max(8 * data["measured_B_outliers_s"].max(), 1e-9)
     assert abs(b["s"] - g["s"]) > tol or b["n_in"] != g["n_in"], "G_own_camera must differ from B_outliers"
+    assert data["J_rounds_n_corr"][0] > 256 and data["J_rounds_n_bad"][0] > 0
+    assert data["K_batch_wide_n_corr"].tolist() == [300, 257, 0, 5] and data["K_batch_wide_n_bad"][0] > 0
+    assert data["K_batch_wide_n_corr"][3] - data["K_batch_wide_n_bad"][3] < 3 and data["K_batch_wide_n_in"][3] == 0
+    assert data["L_round2_wide_n_corr"][0] > 256 and data["L_round2_wide_iters"][0, 1] > 0
     np.savez_compressed(OUT, **data)
     print("wrote", OUT, os.path.getsize(OUT), "bytes")
 

@@ -77,6 +77,17 @@ CASES = {
     # in every case above the reference's gain stop fires in round 1, so its round 2 runs no
     # iteration; with optimize(2) as round 1 the flag stays down and round 2 iterates
     "I_round2": dict(seed=109, n1=96, cands=[(96, 40, 3, 4)], s=1.1, start=(0.2, 0.5, 0.3), opts=dict(its_round1=2)),
+    # the kernel walks the slots, and the culled rows, in rounds of 256: the cases below are the
+    # smallest that enter a second round (J: two slot rounds, rows above 256, the skip rules on
+    # slots >= 256 and undefined slots on both sides of 256), a third, partial one in a batch (K:
+    # more than 256 pairs, exactly 257, none, and fewer than 3 left after the cull) and a round 2
+    # that iterates over more than 256 rows left by the cull (L)
+    "J_rounds": dict(seed=110, n1=400, cands=[(420, 300, 12, 6)], s=1.7, start=(0.02, 0.05, 0.04), skips=True,
+                     skip_from=256, beyond=6, beyond_every=50),
+    "K_batch_wide": dict(seed=111, n1=520, cands=[(540, 300, 12, 6), (530, 257, 0, 4), (520, 0, 0, 0), (520, 5, 3, 1)],
+                         s=0.9, start=(0.02, 0.05, 0.04)),
+    "L_round2_wide": dict(seed=112, n1=400, cands=[(420, 300, 13, 6)], s=1.1, start=(0.2, 0.5, 0.3),
+                          opts=dict(its_round1=2), out_every=24),
 }
 NOISE = 0.15     # pixel noise = NOISE * scale[octave]
 
@@ -130,7 +141,7 @@ def make_case(name):
         undefined, out_left = [], n_out
         for j, i in enumerate(sorted(slots)):
             a = int(cam_a[i])
-            beyond = P.get("beyond", 0) and j % 5 == 2 and len(undefined) < P["beyond"]
+            beyond = P.get("beyond", 0) and j % P.get("beyond_every", 5) == 2 and len(undefined) < P["beyond"]
             i2 = next(k for k in free if k % C == a and ((k >= n1) if beyond else (k < n1)))
             free.remove(i2)
             if beyond:
@@ -141,7 +152,8 @@ def make_case(name):
                 free.remove(m)
             X2 = R12.T @ (X1[i] - t12) / s12
             uv = _in_view(rig, i % C, X2)[1] + rng.normal(0, NOISE * rig["scale"][oct2[i2]] ** -1, 2)
-            if out_left and i not in cross and not beyond:   # gross outliers: the first plain pairs
+            every = P.get("out_every", 1)                    # gross outliers: the first plain pairs, or every n-th
+            if out_left and i not in cross and not beyond and j % every == 0:
                 out_left -= 1
                 uv = uv + rng.choice([-1, 1], 2) * rng.uniform(30, 80, 2)
             xy2[i2] = uv
@@ -149,7 +161,7 @@ def make_case(name):
             first2[m] = i2
             case["matches12"][t, i] = m
         if P.get("skips"):                               # one of each skip rule, on slots not kept
-            spare = [i for i in range(min(n1, n2)) if i not in slots][:4]
+            spare = [i for i in range(P.get("skip_from", 0), min(n1, n2)) if i not in slots][:4]
             ms = [free.pop() for _ in spare]
             for i, m in zip(spare, ms):
                 case["matches12"][t, i] = m

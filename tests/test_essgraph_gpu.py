@@ -5,6 +5,12 @@ lists, iteration and trial counts exact, reals to the tolerance the fixture's me
 runs, a permuted edge list re-sorted to the same bits, the point references resolved on the device,
 a second call on a workspace that allocates nothing, the banded solve against the dense one, and
 the status word for indices out of range.
+
+The one-trial cases (essgraph_cases.ONE_TRIAL) are past one round of every kernel: more than 256
+and more than 16384 edges (2 to 64 chi2 partials, the stride loop), more than 256 keyframes and
+points, 11 to 33 tiles, the loop keyframe off tile 0.  They are held to g2o by the same rule and,
+about ten times tighter, to the host replica's outputs at the same difference step
+(`host_<case>_*`, tolerance from the replica's own spread over its three steps).
 """
 import os
 
@@ -102,20 +108,38 @@ def test_device_entry_equals_the_reference_g2o(gpu, name):
     assert np.array_equal(r["points"][bad], case["pos"][bad])          # :498 a bad point stays
 
 
+ONE_TRIAL = [n for n in ec.CASES if "opts" in ec.CASES[n]]
+
+
+@pytest.mark.parametrize("name", ONE_TRIAL)
+def test_device_entry_equals_the_host_replica_at_the_same_step(gpu, name):
+    """The device and the replica share the difference step and the edge math; summation order and
+    the solver differ.  Tolerance: 8 x the replica's spread over the steps 5e-9, 1e-8, 2e-8."""
+    case = get_case(name)
+    es = _es()
+    band = es.tile_band(case["N"], case["loop"], fixture()[name + "_edges"])
+    print(name, "tile band", band)
+    r = Device(case).run()
+    assert r["status"][0] == 0
+    ec.compare(fixture(), "host_" + name, as_result(r))
+
+
 def test_two_runs_give_identical_bits(gpu):
-    dev = Device(get_case("C_cov40"))
-    same_bits(dev.run(), dev.run())
+    for name in ("C_cov40", "I_dense300"):           # I: 64 chi2 partials, added in index order
+        dev = Device(get_case(name))
+        same_bits(dev.run(), dev.run())
 
 
 def test_permuted_edge_list_is_resorted_to_the_same_bits(gpu):
     """The entry sorts the edges by (v0, v1, kind) before anything is summed, so the order in which
     the caller lists them does not reach a single bit; per-edge outputs follow the caller's order."""
-    dev = Device(get_case("C_cov40"))
-    want = dev.run()
-    perm = np.random.default_rng(5).permutation(len(dev.edges_np))
-    got = dev.run(edges=up(dev.edges_np[perm], np.int32))
-    same_bits(want, got, skip=("edge_chi2",))
-    assert want["edge_chi2"][perm].tobytes() == got["edge_chi2"].tobytes()
+    for name in ("C_cov40", "I_dense300"):
+        dev = Device(get_case(name))
+        want = dev.run()
+        perm = np.random.default_rng(5).permutation(len(dev.edges_np))
+        got = dev.run(edges=up(dev.edges_np[perm], np.int32))
+        same_bits(want, got, skip=("edge_chi2",))
+        assert want["edge_chi2"][perm].tobytes() == got["edge_chi2"].tobytes()
 
 
 def test_point_references_resolved_on_the_device(gpu):
@@ -164,6 +188,19 @@ def test_workspace_call_allocates_nothing_and_equals_the_plain_call(gpu):
         assert host[k].tobytes() == want[k].tobytes(), k
 
 
+def test_workspace_sized_for_the_largest_case_is_reused_for_the_smallest(gpu):
+    """A workspace of exactly J_n300's counts (33 tiles), then A_ring6 (1 tile) and J_n300 again on
+    it: the cached task table changes between the calls, the results are those of the plain calls."""
+    es = _es()
+    big, small = Device(get_case("J_n300")), Device(get_case("A_ring6"))
+    want_big, want_small = big.run(), small.run()
+    ws = es.Workspace(big.case["N"], len(big.edges_np), big.case["P"])
+    same_bits(big.run(ws=ws), want_big)
+    same_bits(small.run(ws=ws), want_small)
+    same_bits(big.run(ws=ws), want_big)
+    ws.close()
+
+
 def test_banded_solve_equals_the_dense_one(gpu):
     """40 keyframes with the edges of neighbours at most two apart: 5 tiles of band 2.  The banded
     factorisation skips only tiles that are zero, so it solves the same systems; the rule's floor,
@@ -180,6 +217,26 @@ def test_banded_solve_equals_the_dense_one(gpu):
         assert np.abs(banded[k] - dense[k]).max() <= 1e-9 * max(1.0, np.abs(dense[k]).max()), k
     narrow = Device(case, e, band=2).run()              # an edge outside the stated band
     assert narrow["status"][0] == -1
+
+
+def test_banded_solve_equals_the_dense_one_at_eleven_tiles(gpu):
+    """G_mid100 as it is: neighbours at most 6 keyframes apart are 11 tiles of band 2 with the fixed
+    keyframe in tile 4; the same rule as above against band = 0.  H_cov130's edges reach across
+    the whole chain: band 2 is refused."""
+    es = _es()
+    case = get_case("G_mid100")
+    e = fixture()["G_mid100_edges"]
+    assert es.tile_band(case["N"], case["loop"], e) == 2
+    banded, dense = Device(case).run(), Device(case, band=0).run()
+    assert banded["status"][0] == 0 and dense["status"][0] == 0 and banded["iterations"][0] == 1
+    assert np.array_equal(banded["trials"], dense["trials"])
+    for k in ("sim3", "pose", "points", "chi2", "edge_chi2"):
+        d = np.abs(banded[k] - dense[k]).max()
+        print("G_mid100 banded - dense", k, d)
+        assert d <= 1e-9 * max(1.0, np.abs(dense[k]).max()), k
+    wide = get_case("H_cov130")
+    assert es.tile_band(wide["N"], wide["loop"], fixture()["H_cov130_edges"]) > 2
+    assert Device(wide, band=2).run()["status"][0] == -1
 
 
 def test_index_out_of_range_is_reported_and_nothing_is_touched(gpu):

@@ -106,6 +106,28 @@ def test_host_program_selects_the_same_edges(host, fix, tmp_path):
     assert np.array_equal(r["edges"], fix["C_cov40_edges"]) and np.array_equal(r["counts"], fix["C_cov40_counts"])
 
 
+def test_one_trial_cases_enter_the_paths_they_are_named_for(built, fix):
+    ONE_TRIAL = [n for n in ec.CASES if "opts" in ec.CASES[n]]
+    tiles = lambda n: (7 * (ec.CASES[n]["N"] - 1) + 63) // 64  # noqa: E731
+    E = {n: len(fix[n + "_edges"]) for n in ONE_TRIAL}
+    assert ONE_TRIAL == ["G_mid100", "H_cov130", "J_n300", "I_dense300"]
+    assert [tiles(n) for n in ONE_TRIAL] == [11, 15, 33, 33]                    # every earlier case has at most 5
+    assert all(256 < E[n] for n in ONE_TRIAL) and E["I_dense300"] > 16384 >= E["J_n300"]
+    assert [min(64, (E[n] + 255) // 256) for n in ONE_TRIAL] == [3, 3, 35, 64]  # chi2 partials
+    loop = ec.CASES["G_mid100"]["loop"]
+    assert 0 < 7 * loop // 64 < tiles("G_mid100") - 1                           # the fixed keyframe in a middle tile
+    assert ec.CASES["J_n300"]["N"] > 256 and ec.CASES["J_n300"]["P"] > 256
+    assert fix["H_cov130_counts"].tolist()[:3] == [4, 129, 1]                   # loop connections, tree, earlier loop
+    es = _es()
+    band = {n: es.tile_band(ec.CASES[n]["N"], ec.CASES[n].get("loop", 0), fix[n + "_edges"]) for n in ONE_TRIAL}
+    assert band == {"G_mid100": 2, "H_cov130": 15, "J_n300": 5, "I_dense300": 8}, band      # H: every tile filled
+    for n in ONE_TRIAL:
+        assert fix[n + "_trials"].tolist() == [1] and fix[n + "_chi2"][0] < fix[n + "_chi2_initial"]
+        assert fix["host_" + n + "_trials"].tolist() == [1]
+        for f in ec.REALS:                      # the second tier is the tighter one
+            assert fix["measured_host_%s_%s" % (n, f)] < fix["measured_%s_%s" % (n, f)], (n, f)
+
+
 def _tiny(cov, lc, loops=None, parent=None, has_corr=None, cur=3, loop=0, ids=(10, 20, 30, 40)):
     N = len(ids)
     cp, cf = ec._csr(cov)
@@ -217,3 +239,19 @@ def test_fixture_regenerates_from_the_reference_g2o(fix, tmp_path):
     spread = gen.check_and_measure("B_ring12", runs)
     for f in ec.REALS:
         assert spread[f] == float(fix["measured_B_ring12_" + f]), f
+    # a one-trial case: the reference runs, the generator's conditions, and the host replica's keys
+    name = "G_mid100"
+    case = ec.make_case(name)
+    runs = gen.run_reference(exe, case, str(tmp_path))
+    for f in ec.INTS + ec.REALS:
+        assert np.array_equal(np.asarray(runs[0][f]), fix["%s_%s" % (name, f)]), f
+    spread = gen.check_and_measure(name, runs)
+    for f in ec.REALS:
+        assert spread[f] == float(fix["measured_%s_%s" % (name, f)]), f
+    assert gen.one_trial(case) and gen.check_one_trial(name, case, runs, spread) >= 0.9
+    hruns = gen.run_host(gen.build_host(str(tmp_path)), case, str(tmp_path))
+    hspread = gen.spread_of(hruns)
+    for f in ("iterations", "trials") + ec.REALS:
+        assert np.array_equal(np.asarray(hruns[0][f]), fix["host_%s_%s" % (name, f)]), f
+    for f in ec.REALS:
+        assert hspread[f] == float(fix["measured_host_%s_%s" % (name, f)]), f

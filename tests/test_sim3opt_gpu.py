@@ -92,18 +92,20 @@ def test_device_entry_equals_the_reference_g2o(gpu, name):
 
 
 def test_a_candidate_alone_equals_the_batch_bit_for_bit(gpu):
-    case = get_case("C_batch")
-    out, m12 = Device(case).run()
-    for t in range(len(case["kf2s"])):
-        one, m1 = Device(case, [t]).run()
-        for k in out:
-            assert one[k][0].tobytes() == out[k][t].tobytes(), (t, k)
-        assert np.array_equal(m1[0], m12[t])
+    for name in ("C_batch", "K_batch_wide"):         # K: three slot rounds, candidates of 300 / 257 / 0 / 5 pairs
+        case = get_case(name)
+        out, m12 = Device(case).run()
+        for t in range(len(case["kf2s"])):
+            one, m1 = Device(case, [t]).run()
+            for k in out:
+                assert one[k][0].tobytes() == out[k][t].tobytes(), (name, t, k)
+            assert np.array_equal(m1[0], m12[t]), (name, t)
 
 
 def test_two_runs_give_identical_bits(gpu):
-    dev = Device(get_case("B_outliers"))
-    same_bits(dev.run(), dev.run())
+    for name in ("B_outliers", "K_batch_wide"):
+        dev = Device(get_case(name))
+        same_bits(dev.run(), dev.run())
 
 
 def test_workspace_and_host_form_equal_the_plain_call(gpu):

@@ -59,6 +59,34 @@ def test_cases_cover_what_their_names_say(fix):
     assert fix["F_gainstop_iters"][0, 1] == 0 and fix["I_round2_iters"][0, 1] > 0
     assert fix["H_undefined_n_undefined"][0] == 6
     assert fix["G_own_camera_n_bad"][0] != fix["B_outliers_n_bad"][0]
+    # the cases named for the kernel's rounds of 256 slots / 256 rows, on the fixture alone
+    rows = {}
+    for name in ("J_rounds", "K_batch_wide", "L_round2_wide"):
+        for t in range(len(fix[name + "_n_corr"])):
+            kept = ~np.isnan(fix[name + "_edge_chi2"][t][:, 0])
+            assert kept.sum() == fix[name + "_n_corr"][t]
+            culled = kept & (fix[name + "_matches12"][t] < 0)
+            rows[name, t] = (np.flatnonzero(kept), (np.cumsum(kept) - 1)[culled])
+    for name, t, rounds in (("J_rounds", 0, 2), ("K_batch_wide", 0, 3), ("K_batch_wide", 1, 3), ("L_round2_wide", 0, 2)):
+        slots = rows[name, t][0]
+        assert len(slots) > 256, (name, t)
+        for r in range(rounds):                 # kept slots in every round of 256, so `base` carries a row offset
+            assert ((slots >= 256 * r) & (slots < 256 * (r + 1))).any(), (name, t, r)
+    assert fix["J_rounds_n_bad"][0] > 0 and fix["J_rounds_n_undefined"][0] == 6
+    case = sc.make_case("J_rounds")
+    undef = np.array(case["undefined"][0])
+    assert (undef < 256).any() and (undef >= 256).any()
+    skipped = np.flatnonzero((case["matches12"][0] >= 0) & np.isnan(fix["J_rounds_edge_chi2"][0][:, 0]))
+    skipped = np.setdiff1d(skipped, undef)      # the four skip rules: matched, defined and not kept
+    assert len(skipped) == 4 and (skipped >= 256).all(), skipped
+    assert fix["K_batch_wide_n_corr"].tolist() == [300, 257, 0, 5] and fix["K_batch_wide_n_bad"][0] > 0
+    assert fix["K_batch_wide_n_in"][2] == 0 and (fix["K_batch_wide_iters"][2] == 0).all()
+    assert fix["K_batch_wide_n_corr"][3] - fix["K_batch_wide_n_bad"][3] < 3 and fix["K_batch_wide_n_in"][3] == 0
+    assert sc.make_case("K_batch_wide")["matches12"].shape == (4, 520)          # three slot rounds, the last partial
+    assert fix["L_round2_wide_iters"][0, 1] > 0
+    culled = rows["L_round2_wide", 0][1]        # pairs taken out in both rounds of 256 rows of the cull loop
+    assert (culled < 256).any() and (culled >= 256).any(), culled
+    assert fix["L_round2_wide_n_in"][0] > 256   # round 2 iterates over more live rows than one round
     for name in sc.CASES:                       # a Sim3 returned before the recover is the input
         case = sc.make_case(name)
         for t in range(len(case["kf2s"])):

@@ -227,8 +227,10 @@ def host_find(case, n_it, flags, state=None, good=None):
 def test_correspondence_counts_with_find(gpu, N):
     """Candidate 0 has exactly N correspondences, beside companions of 40 and 20, through find
     (n_iterations = the cap), device entry and host entry: N below / at / above min_inliers, the
-    wave and chunk boundaries of the check kernel, max_its 0, 1, 3, 288 (below the cap) and 300 (at
-    it).  Every batch must show all five coverage conditions."""
+    64-lane wave boundaries of the check kernel (63, 64, 65, 129), its staging chunks of 256
+    correspondences (255, 256, 257, and 513 in a third chunk), the prepare kernel's rounds of 1024
+    slots and rows (1030 of 1110 slots), max_its 0, 1, 3, 288 (below the cap) and 300 (at it).
+    Every batch must show all five coverage conditions."""
     case = boundary_case(N)
     good = np_good_flags(case, N)
     dev = Device(case, good=good)
@@ -242,7 +244,8 @@ def test_correspondence_counts_with_find(gpu, N):
     th.check(out, CAP, good)
     th.done()
     assert tr.its == th.its and tr.best == th.best
-    assert tr.max_its[0] == {0: 0, 14: 0, 15: 1, 16: 3, 63: 288}.get(N, CAP)
+    assert tr.max_its[0] == {0: 0, 14: 0, 15: 1, 16: 3, 63: 288, 64: 300, 65: 300, 129: 300, 255: 300, 256: 300,
+                             257: 300, 513: 300, 1030: 300}[N]
 
 
 @pytest.mark.parametrize("seed", CTOR_SEEDS)
@@ -395,6 +398,26 @@ def test_malformed_samples_and_rows_stay_inside_the_buffers(gpu):
     n1 = len(case["kf1"]["kp_xy"])
     assert out["max_its"][0] == np_max_its(n1)[0] and ((out["hyp_inl"][0] >= -1) & (out["hyp_inl"][0] <= n1)).all()
     assert not out["success"][0] or out["inlier"][0][case["rows"][0]["idx1"][:50:2]].sum() == 0
+    # the same with 1110 slots and 1030 rows: samples, cameras and the count of rows past the first
+    # staging chunk (256) and past the first round of the prepare kernel (1024)
+    case = boundary_case(1030)
+    N, n1 = case["rows"][0]["n"], len(case["kf1"]["kp_xy"])
+    assert N == 1030 and n1 > 1024
+    bad = case["samples"].copy()
+    bad[0, :40:3, 0], bad[0, 1:40:3, 1], bad[0, 2:40:3, 2] = -7, 1 << 30, N
+    dev = Device(case, samples=bad)
+    same_rows(case, dev.rows())
+    out = dev.iterate(CAP, ss.INIT)
+    assert ((out["hyp_inl"][0] >= -1) & (out["hyp_inl"][0] <= N)).all()
+    dev = Device(case)
+    dev.gc.t["cam1"][0, 200:N:2] = 9
+    dev.gc.t["cam2"][0, 201:N:4] = -1
+    dev.gc.t["n"][0] = 1 << 20
+    torch.cuda.synchronize()
+    out = dev.iterate(CAP, ss.INIT)
+    assert out["max_its"][0] == np_max_its(n1)[0] and ((out["hyp_inl"][0] >= -1) & (out["hyp_inl"][0] <= n1)).all()
+    hit = case["rows"][0]["idx1"][200:N:2]
+    assert (hit >= 1024).any() and (not out["success"][0] or out["inlier"][0][hit].sum() == 0)
 
 
 def test_argument_errors_of_the_device_entries(gpu):

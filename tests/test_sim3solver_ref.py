@@ -387,6 +387,12 @@ CASES = {"t1_n50": dict(seed=11, Ns=(50,), inlier=(0.55,)),
 # hit and a candidate without one.  The seeds are checked on the CPU by
 # test_boundary_batches_are_not_vacuous (coverage, no unsure decision, stage-A exclusions).
 BOUNDARY = {0: 101, 14: 240, 15: 250, 16: 260, 63: 730, 64: 740, 65: 750, 129: 1390}
+# The check kernel stages the correspondences in chunks of 256 (one below, at, one above, and a
+# third chunk); the prepare kernel walks the slots and moves the rows in rounds of 1024: N = 1030 of
+# 1110 slots is a second slot round, a second row round and a fifth chunk.
+BOUNDARY.update({255: 2550, 256: 2560, 257: 2570, 513: 5130, 1030: 10302})
+PER_CAM = {255: 200, 256: 200, 257: 200, 513: 200, 1030: 370}          # keypoints per camera where 60 cannot hold N
+K_CHUNK, K_PREP = 256, 1024
 _CACHE = {}
 
 
@@ -398,7 +404,8 @@ def get_case(name):
 
 def boundary_case(N):
     if ("b", N) not in _CACHE:
-        _CACHE["b", N] = make_solver_case(seed=BOUNDARY[N], Ns=(N, 40, 20), n_per_cam=60, inlier=(0.55, 0.55, 0.3))
+        _CACHE["b", N] = make_solver_case(seed=BOUNDARY[N], Ns=(N, 40, 20), n_per_cam=PER_CAM.get(N, 60),
+                                          inlier=(0.55, 0.55, 0.3))
     return _CACHE["b", N]
 
 
@@ -748,6 +755,15 @@ def test_boundary_batches_are_not_vacuous(N):
     assert sum(int(ch[1].sum()) for s in sols for ch in s["checks"]) == 0
     assert excluded_within_limit(c)
     assert [s["max_its"] for s in sols][1:] == [np_max_its(40)[0], np_max_its(20)[0]]
+    if N > K_PREP:
+        # kept rows from slots on both sides of slot 1024; matched slots dropped below it, so the row
+        # offset carried into the second slot round is not the slot offset, and at or above it, so
+        # the second round compacts as well
+        idx1, m = c["rows"][0]["idx1"], c["matches12"][0]
+        assert (idx1 < K_PREP).any() and (idx1 >= K_PREP).any()
+        dropped = np.setdiff1d(np.flatnonzero(m >= 0), idx1)
+        assert (dropped >= K_PREP).any() and (dropped < K_PREP).any(), dropped
+        assert len(m) > K_PREP and (N + K_CHUNK - 1) // K_CHUNK == 5
 
 
 N_SINGLE = 40       # visits of one iteration: enough that the two scripted repeats stay under 10 %
