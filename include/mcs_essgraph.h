@@ -112,6 +112,86 @@ int mcs_optimize_essential_graph(int32_t device, int32_t N, const double* Scw, c
                                  const int32_t* point_ref, const uint8_t* point_bad,
                                  const mcs_essgraph_options* opts, const mcs_essgraph_out* out);
 
+/* ---- The block-sparse path: maps beyond the 878 keyframes of the entries above ----------------
+ *
+ * A plan is made on the host from the edge list, once per loop closure (the one host-synchronous
+ * step, beside mcs_essgraph_select_edges): the graph of the free keyframes (the fixed loop
+ * keyframe left out, a pair that carries several edges counted once), a nested-dissection ordering
+ * by breadth-first level sets, the pattern of L in 7 x 7 blocks, its supernodes (the separators
+ * and leaves) and their levels.  The plan is canonical: a permuted edge list gives the same plan
+ * (equal digest).  It owns its device copies and all numeric storage (the assembled system and L
+ * in the pattern of L, the right-hand sides, and the per-call buffers sized by max_edges and
+ * max_points): a call on a plan allocates nothing.
+ *
+ * Limits, from arithmetic on counts and not from 878: every index is an int32; max_edges < 2^31 /
+ * 112; one copy of the pattern of L (the supernodes' dense panels, 392 bytes per block) holds at
+ * most 1 GiB, and the plan keeps three.  Above that plan_create returns MCS_ERR_UNSUPPORTED.
+ * device < 0 makes a host-only plan: info and arrays, no device storage, not accepted by
+ * mcs_optimize_essential_graph_planned_device. */
+typedef struct mcs_essgraph_plan_options {
+  int32_t leaf_size;   /* the dissection stops at this many keyframes; 0 = the default, 4 */
+} mcs_essgraph_plan_options;
+void mcs_essgraph_plan_default_options(mcs_essgraph_plan_options* o);
+
+typedef struct mcs_essgraph_plan mcs_essgraph_plan;
+/* edges [n_edges][3] on the host, as mcs_essgraph_select_edges leaves them.  max_edges (raised to
+ * n_edges) and max_points size the per-call buffers; options may be null. */
+int mcs_essgraph_plan_create(int32_t device, int32_t n_kf, int32_t loop_index, const int32_t* edges, int32_t n_edges,
+                             int32_t max_edges, int32_t max_points, const mcs_essgraph_plan_options* options,
+                             mcs_essgraph_plan** out);
+void mcs_essgraph_plan_destroy(mcs_essgraph_plan* plan);
+
+typedef struct mcs_essgraph_plan_info {
+  int32_t n_kf, loop_index;
+  int32_t free_blocks;                /* n_kf - 1 block rows */
+  int32_t leaf_size, supernodes, levels;
+  int32_t max_supernode_columns;      /* block columns of the widest supernode */
+  int32_t solver_launches_per_trial;  /* factor (with the forward solve) + backward solve */
+  int32_t launches_per_trial;         /* all launches of one LM trial */
+  int64_t a_blocks;                   /* lower blocks of A: the diagonals and the planned pairs */
+  int64_t l_blocks;                   /* lower blocks of L; l_blocks / a_blocks is the fill ratio */
+  int64_t panel_blocks;               /* blocks stored (the panels' upper triangles included) */
+  int64_t flops_per_factor;
+  int64_t device_bytes;               /* 0 for a host-only plan */
+  uint64_t digest;                    /* FNV-1a over every array of the plan */
+} mcs_essgraph_plan_info;
+int mcs_essgraph_plan_get_info(const mcs_essgraph_plan* plan, mcs_essgraph_plan_info* info);
+
+/* The plan's host arrays, valid until the plan is destroyed.  S = supernodes.  Supernode s owns
+ * the columns col0[s] .. col0[s + 1] - 1 of the permuted matrix; rows[row_ptr[s] .. row_ptr[s + 1])
+ * are its block rows (its own columns, then the rows below, ascending): the pattern of L. */
+typedef struct mcs_essgraph_plan_arrays {
+  const int32_t* perm;      /* [free_blocks] free keyframe -> column of the permuted matrix */
+  const int32_t* col0;      /* [S + 1] */
+  const int32_t* row_ptr;   /* [S + 1] */
+  const int32_t* rows;      /* [n_rows] */
+  int32_t n_rows;
+  const int32_t* parent;    /* [S] supernodal tree, -1 = a root */
+  const int32_t* level;     /* [S] height in the tree = the launch it runs in */
+  const int32_t* block_off; /* [S + 1] first stored block of a supernode: row position p, own column c
+                               is block block_off[s] + p * columns(s) + c */
+  const uint8_t* a_block;   /* [panel_blocks] 1 = a block of A */
+} mcs_essgraph_plan_arrays;
+int mcs_essgraph_plan_get_arrays(const mcs_essgraph_plan* plan, mcs_essgraph_plan_arrays* arrays);
+
+/* mcs_optimize_essential_graph_device with the plan's solver.  opts->tile_band is ignored.
+ * Stream-ordered, no host synchronisation, no allocation.  out->status: MCS_ERR_ARG also when N
+ * or loop_index are not the plan's or an edge joins two free keyframes whose pair the plan does
+ * not hold (nothing else is written); never MCS_ERR_HIP, the path has no hand-off wait.  E above
+ * max_edges or P above max_points return MCS_ERR_ARG before any device use. */
+int mcs_optimize_essential_graph_planned_device(mcs_essgraph_plan* plan, int32_t N, const double* d_Scw,
+                                                const double* d_Snc, int32_t loop_index, int32_t E,
+                                                const int32_t* d_edges, int32_t P, double* d_point_pos,
+                                                const int32_t* d_point_ref, const uint8_t* d_point_bad,
+                                                const mcs_essgraph_options* opts, const mcs_essgraph_out* out,
+                                                void* stream);
+
+/* The same on host buffers (out holds host pointers): plans, copies, runs, waits. */
+int mcs_optimize_essential_graph_sparse(int32_t device, int32_t N, const double* Scw, const double* Snc,
+                                        int32_t loop_index, int32_t E, const int32_t* edges, int32_t P,
+                                        double* point_pos, const int32_t* point_ref, const uint8_t* point_bad,
+                                        const mcs_essgraph_options* opts, const mcs_essgraph_out* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -644,3 +644,6 @@ int mcs_optimize_essential_graph(int32_t device, int32_t N, const double* Scw, c
 }
 
 }  // extern "C"
+
+// the block-sparse path over a plan (the mcs_essgraph_plan entries)
+#include "essential_graph_sparse.hpp"

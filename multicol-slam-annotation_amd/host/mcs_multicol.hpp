@@ -811,11 +811,19 @@ struct EssentialGraphPoints {            // GetAllMapPoints()
   std::vector<int64_t> corrected_by, corrected_ref, ref_kf;   // mnCorrectedByKF, mnCorrectedReference, reference mnId
   std::vector<uint8_t> bad;
 };
-struct EssentialGraphReport { int32_t iterations = 0, n_edges = 0, counts[4] = {0, 0, 0, 0}; double chi2 = 0, lambda = 0; };
+struct EssentialGraphReport {
+  int32_t iterations = 0, n_edges = 0, counts[4] = {0, 0, 0, 0};
+  double chi2 = 0, lambda = 0;
+  bool sparse = false;                   // the block-sparse solver ran (mcs_optimize_essential_graph_sparse)
+};
+// Auto: the dense solver wherever it takes the map (every result it gives keeps its bits), the
+// block-sparse one where it answers MCS_ERR_UNSUPPORTED (more than 878 keyframes).
+enum class EssentialGraphSolver { Auto, Dense, Sparse };
 
 inline EssentialGraphReport OptimizeEssentialGraph(std::vector<EssentialGraphKeyFrame>& kfs, EssentialGraphPoints& pts,
                                                    int loop_index, int cur_index,
-                                                   const mcs_essgraph_options* options = nullptr, int device = 0) {
+                                                   const mcs_essgraph_options* options = nullptr, int device = 0,
+                                                   EssentialGraphSolver solver = EssentialGraphSolver::Auto) {
   const int N = (int)kfs.size(), P = (int)pts.bad.size();
   if (N < 1 || loop_index < 0 || loop_index >= N || cur_index < 0 || cur_index >= N)
     throw std::invalid_argument("OptimizeEssentialGraph: loop / current keyframe outside the list");
@@ -887,11 +895,14 @@ inline EssentialGraphReport OptimizeEssentialGraph(std::vector<EssentialGraphKey
   mcs_essgraph_out out{nullptr, nullptr, pose.data(), &rep.iterations, nullptr, chi2.data(), &rep.lambda, nullptr, &status};
   pts.pos.resize(3 * (size_t)P + 3);
   pts.bad.resize((size_t)P + 1);
-  rc = mcs_optimize_essential_graph(device, N, Scw.data(), Snc.data(), loop_index, E, edges.data(), P, pts.pos.data(),
-                                    ref.data(), pts.bad.data(), &o, &out);
+  rep.sparse = solver == EssentialGraphSolver::Sparse ||
+               (solver == EssentialGraphSolver::Auto && mcs_essgraph_supported(N, o.tile_band) == MCS_ERR_UNSUPPORTED);
+  rc = (rep.sparse ? mcs_optimize_essential_graph_sparse : mcs_optimize_essential_graph)(
+      device, N, Scw.data(), Snc.data(), loop_index, E, edges.data(), P, pts.pos.data(), ref.data(), pts.bad.data(), &o,
+      &out);
   pts.pos.resize(3 * (size_t)P);
   pts.bad.resize((size_t)P);
-  check(rc, "mcs_optimize_essential_graph");
+  check(rc, rep.sparse ? "mcs_optimize_essential_graph_sparse" : "mcs_optimize_essential_graph");
   for (int i = 0; i < N; i++) std::memcpy(kfs[i].pose, &pose[16 * (size_t)i], 16 * sizeof(double));
   rep.chi2 = rep.iterations > 0 ? chi2[rep.iterations - 1] : 0.0;
   return rep;

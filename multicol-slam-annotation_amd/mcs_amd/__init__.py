@@ -203,6 +203,15 @@ SIGNATURES = {
     "mcs_optimize_essential_graph_device": (ctypes.c_int, [_P, _I32, _P, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P,
                                                             _P]),
     "mcs_optimize_essential_graph": (ctypes.c_int, [_I32, _I32, _P, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P]),
+    "mcs_essgraph_plan_default_options": (None, [_P]),
+    "mcs_essgraph_plan_create": (ctypes.c_int, [_I32, _I32, _I32, _P, _I32, _I32, _I32, _P, _P]),
+    "mcs_essgraph_plan_destroy": (None, [_P]),
+    "mcs_essgraph_plan_get_info": (ctypes.c_int, [_P, _P]),
+    "mcs_essgraph_plan_get_arrays": (ctypes.c_int, [_P, _P]),
+    "mcs_optimize_essential_graph_planned_device": (ctypes.c_int, [_P, _I32, _P, _P, _I32, _I32, _P, _I32, _P, _P, _P,
+                                                                    _P, _P, _P]),
+    "mcs_optimize_essential_graph_sparse": (ctypes.c_int, [_I32, _I32, _P, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P,
+                                                            _P]),
     # CreateNewMapPoints (include/mcs_newpoints.h; wrappers in mcs_amd/new_points.py)
     "mcs_newpts_workspace_create": (ctypes.c_int, [_I32, _I32, _P]),
     "mcs_newpts_workspace_destroy": (None, [_P]),

@@ -12,6 +12,12 @@ src/cLoopClosing.cpp:648).
   resolve_point_refs_device(kf_id, corrected_by, corrected_ref, ref_kf, current_id)
         the keyframe index per point (:501-507) on torch tensors
 
+  Plan(n_kf, loop, edges, max_edges=None, max_points=0, leaf_size=None, device=0)
+        the block-sparse solver's plan for one edge list (any number of keyframes); .info, .arrays()
+  optimize_planned_device(plan, Scw, Snc, edges, point_pos, point_ref, point_bad, options, out=None)
+        optimize_device with the plan's solver
+  optimize_sparse(Scw, Snc, loop, edges, ...)     optimize() with a plan made for the call
+
 Keyframes come in ascending id order and none is bad.  A Sim3 is 8 doubles: s, qw qx qy qz,
 tx ty tz.  Scw holds CorrectedSim3 where present, else Sim3(R, t, 1) of the inverse pose; Snc
 NonCorrectedSim3 where present, else Scw.  A CSR argument is (ptr, idx) or (ptr, idx, weight).
@@ -187,6 +193,120 @@ def optimize(Scw, Snc, loop, edges, point_pos=None, point_ref=None, point_bad=No
     return dict(arrs, points=pos)
 
 
-__all__ = ["EssGraphMap", "EssGraphOptions", "EssGraphOut", "Workspace", "default_options", "out_shapes", "select_edges",
+class PlanOptions(ctypes.Structure):
+    """Mirror of mcs_essgraph_plan_options."""
+    _fields_ = [("leaf_size", ctypes.c_int32)]
+
+
+class PlanInfo(ctypes.Structure):
+    """Mirror of mcs_essgraph_plan_info."""
+    _fields_ = [(k, ctypes.c_int32) for k in ("n_kf", "loop_index", "free_blocks", "leaf_size", "supernodes", "levels",
+                                              "max_supernode_columns", "solver_launches_per_trial",
+                                              "launches_per_trial")] + \
+               [(k, ctypes.c_int64) for k in ("a_blocks", "l_blocks", "panel_blocks", "flops_per_factor",
+                                              "device_bytes")] + [("digest", ctypes.c_uint64)]
+
+
+class PlanArrays(ctypes.Structure):
+    """Mirror of mcs_essgraph_plan_arrays."""
+    _fields_ = [("perm", ctypes.c_void_p), ("col0", ctypes.c_void_p), ("row_ptr", ctypes.c_void_p),
+                ("rows", ctypes.c_void_p), ("n_rows", ctypes.c_int32), ("parent", ctypes.c_void_p),
+                ("level", ctypes.c_void_p), ("block_off", ctypes.c_void_p), ("a_block", ctypes.c_void_p)]
+
+
+class Plan:
+    """mcs_essgraph_plan: the block-sparse LDL^T planned on the host for one edge list, with the
+    device storage of its calls.  edges int32 [E, 3] on the host.  device < 0: a host-only plan
+    (info and arrays).  .info: dict of mcs_essgraph_plan_info, with `fill` = l_blocks / a_blocks."""
+
+    def __init__(self, n_kf, loop, edges, max_edges=None, max_points=0, leaf_size=None, device=0):
+        e = np.ascontiguousarray(edges, np.int32).reshape(-1, 3)
+        o = PlanOptions()
+        lib().mcs_essgraph_plan_default_options(ctypes.byref(o))
+        if leaf_size is not None:
+            o.leaf_size = int(leaf_size)
+        h = ctypes.c_void_p()
+        _check(lib().mcs_essgraph_plan_create(int(device), int(n_kf), int(loop), e.ctypes.data if len(e) else None, len(e),
+                                              len(e) if max_edges is None else int(max_edges), int(max_points),
+                                              ctypes.byref(o), ctypes.byref(h)))
+        self._h, self.device, self.n_kf, self.loop = h, int(device), int(n_kf), int(loop)
+        i = PlanInfo()
+        _check(lib().mcs_essgraph_plan_get_info(h, ctypes.byref(i)))
+        self.info = {k: int(getattr(i, k)) for k, _ in PlanInfo._fields_}
+        self.info["fill"] = self.info["l_blocks"] / max(1, self.info["a_blocks"])
+
+    def arrays(self):
+        """Copies of the plan's host arrays (mcs_essgraph_plan_arrays) by name."""
+        a = PlanArrays()
+        _check(lib().mcs_essgraph_plan_get_arrays(self._h, ctypes.byref(a)))
+        S, n = self.info["supernodes"], self.info["free_blocks"]
+
+        def arr(ptr, count, ct, dt):
+            if count == 0:
+                return np.zeros(0, dt)
+            return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ct)), (count,)).astype(dt, copy=True)
+        i32 = lambda ptr, count: arr(ptr, count, ctypes.c_int32, np.int32)  # noqa: E731
+        return dict(perm=i32(a.perm, n), col0=i32(a.col0, S + 1), row_ptr=i32(a.row_ptr, S + 1),
+                    rows=i32(a.rows, a.n_rows), parent=i32(a.parent, S), level=i32(a.level, S),
+                    block_off=i32(a.block_off, S + 1),
+                    a_block=arr(a.a_block, self.info["panel_blocks"], ctypes.c_uint8, np.uint8))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().mcs_essgraph_plan_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def optimize_planned_device(plan, Scw, Snc, edges, point_pos, point_ref, point_bad, options=None, out=None, loop=None):
+    """mcs_optimize_essential_graph_planned_device on torch tensors, stream-ordered; as
+    optimize_device, with the plan's solver (options.tile_band is ignored).  loop defaults to the
+    plan's."""
+    o = options if options is not None else default_options()
+    N, E = int(Scw.shape[0]), int(edges.shape[0])
+    P = int(point_pos.shape[0]) if point_pos is not None else 0
+    if out is None:
+        out = new_out(N, E, plan.device)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    _check(lib().mcs_optimize_essential_graph_planned_device(plan._h, N, ptr(Scw), ptr(Snc),
+                                                             plan.loop if loop is None else int(loop), E, ptr(edges), P,
+                                                             ptr(point_pos), ptr(point_ref), ptr(point_bad),
+                                                             ctypes.byref(o), ctypes.byref(out[0]),
+                                                             _stream(plan.device)))
+    return out[1]
+
+
+def optimize_sparse(Scw, Snc, loop, edges, point_pos=None, point_ref=None, point_bad=None, options=None, device=0):
+    """mcs_optimize_essential_graph_sparse: optimize() through a plan made for the call; any number
+    of keyframes the plan's limits take."""
+    Scw = np.ascontiguousarray(Scw, np.float64).reshape(-1, 8)
+    Snc = np.ascontiguousarray(Snc, np.float64).reshape(-1, 8)
+    edges = np.ascontiguousarray(edges, np.int32).reshape(-1, 3)
+    N, E = len(Scw), len(edges)
+    pos = np.ascontiguousarray(point_pos if point_pos is not None else np.zeros((0, 3)), np.float64).reshape(-1, 3).copy()
+    P = len(pos)
+    ref = np.ascontiguousarray(point_ref if point_ref is not None else np.zeros(0), np.int32).reshape(-1)
+    bad = np.ascontiguousarray(point_bad if point_bad is not None else np.zeros(0), np.uint8).reshape(-1)
+    if len(Snc) != N or len(ref) != P or len(bad) != P:
+        raise ValueError("optimize_sparse: Scw / Snc and the point arrays must agree in length")
+    o = options if isinstance(options, EssGraphOptions) else default_options(**(options or {}))
+    out, arrs = EssGraphOut(), {}
+    for k, (dt, shp) in out_shapes(N, E).items():
+        arrs[k] = np.zeros(shp, dt)
+        setattr(out, k, arrs[k].ctypes.data)
+    _check(lib().mcs_optimize_essential_graph_sparse(int(device), N, Scw.ctypes.data, Snc.ctypes.data, int(loop), E,
+                                                     edges.ctypes.data if E else None, P, pos.ctypes.data if P else None,
+                                                     ref.ctypes.data if P else None, bad.ctypes.data if P else None,
+                                                     ctypes.byref(o), ctypes.byref(out)))
+    return dict(arrs, points=pos)
+
+
+__all__ = ["Plan", "PlanOptions", "PlanInfo", "PlanArrays", "optimize_planned_device", "optimize_sparse",
+           "EssGraphMap", "EssGraphOptions", "EssGraphOut", "Workspace", "default_options", "out_shapes", "select_edges",
            "tile_band", "supported", "new_out", "resolve_point_refs_device", "optimize_device", "optimize",
            "MAX_ITERATIONS", "McsError"]
