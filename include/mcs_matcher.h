@@ -22,6 +22,7 @@
 
 #include <stdint.h>
 #include "mcs_common.h"
+#include "mcs_extractor.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -138,10 +139,18 @@ int mcs_check_dist_epipolar_line(const double* ray1, const double* ray2, const d
  *   SearchForInitialization(F1, F2, ...)            src/cORBmatcher.cpp:579-726  (rule 2)
  *   WindowSearch(F1, F2, windowSize, ...)           src/cORBmatcher.cpp:326-473  (rule 3)
  * with checkOrientation = false (include/cORBmatcher.h:40).
- * Split: the grid is built on the host (it is part of the cMultiFrame constructor); the
- * device enumerates every query's window candidates in the reference's order (cells ix-major,
- * then iy, then insertion order) and computes their Hamming distances; the host applies the
- * reference's sequential selection rule (it depends on earlier queries' assignments). */
+ * Split: two forms over the same candidate walk (cells ix-major, then iy, then insertion
+ * order; the Hamming distance of every candidate), which give the same bits.
+ *   Host-split form (mcs_frame_grid_build, mcs_window_search_device, mcs_window_select,
+ *   mcs_window_match): the grid is built on the host (it is part of the cMultiFrame
+ *   constructor), the device enumerates the candidates, the host applies the reference's
+ *   sequential selection rule (it depends on earlier queries' assignments).  Serves all four
+ *   rules; the search synchronises once and the candidate lists are downloaded.
+ *   Device form (mcs_track_*, mcs_frame_grid_build_device; rules 0, 1 and 3): grid, queries,
+ *   candidates and the ordered selection all run stream-ordered on the device over a
+ *   workspace, with no allocation, no synchronisation and no copy to the host; capacity
+ *   overflow is reported in device memory (d_status).  Rule 2 un-matches earlier queries and
+ *   runs once per session: it stays with the host-split form. */
 #define MCS_GRID_COLS 64
 #define MCS_GRID_ROWS 48
 
@@ -203,6 +212,150 @@ int mcs_window_match(int32_t device, int32_t rule, const mcs_window_frame* frame
                      const double* q_xyr, const int32_t* q_cam_lvl, const uint8_t* q_desc,
                      const uint8_t* q_mask, int32_t th, double nnratio, uint8_t* kp_assigned,
                      int32_t* match, int32_t* n_matches);
+
+/* -- Device form: the windowed matchers of tracking with nothing downloaded ---------------
+ *   TrackWithMotionModel -> SearchByProjection(Current, Last)      (rule 1)
+ *   TrackLocalMap        -> isInFrustum + SearchByProjection(F, MPs) (rule 0)
+ *   TrackPreviousFrame   -> WindowSearch                           (rule 3)
+ * Every d_ pointer is device memory and every call is asynchronous on `stream`.  A workspace
+ * serves one stream at a time. */
+#define MCS_TRACK_MAX_CAMS 8
+#define MCS_TRACK_OVERFLOW 1            /* d_status[1] bit 0: candidates exceeded cand_cap */
+#define MCS_TRACK_ROUNDS(flags) ((int32_t)((uint64_t)(flags) >> 32))   /* settle rounds of the call */
+
+/* Workspace of the device form: grid-build scratch, the candidate lists (cand_cap entries)
+ * and the selection's marks and query lists, for frames of at most max_kp keypoint slots and
+ * calls of at most max_queries queries. */
+typedef struct mcs_track_workspace mcs_track_workspace;
+int mcs_track_workspace_create(int32_t device, int32_t max_kp, int32_t max_queries,
+                               int64_t cand_cap, mcs_track_workspace** out);
+void mcs_track_workspace_destroy(mcs_track_workspace* ws);
+
+/* mcs_frame_grid_build on the device, bit-identical for finite coordinates whose grid
+ * position fits an int (beyond that the host's lrint and the device's saturating conversion
+ * part): the same PosInGrid arithmetic (float subtraction, cvRound of the double product),
+ * keypoints outside the grid or with a camera outside [0, n_cams) dropped, ascending keypoint
+ * index within a cell.  d_kp_xy [cap][2],
+ * d_kp_cam [cap]; d_n_kp = the keypoint count on the device (clamped to [0, cap]; slots past
+ * it are not read), NULL = cap.  Out: d_cell_ptr [n_cams*64*48 + 1], d_cell_kp [cap],
+ * d_n_in_grid (nullable).  cap <= the workspace's max_kp, n_cams <= MCS_TRACK_MAX_CAMS. */
+int mcs_frame_grid_build_device(mcs_track_workspace* ws, const float* d_kp_xy,
+                                const int32_t* d_kp_cam, const int32_t* d_n_kp, int32_t cap,
+                                int32_t n_cams, const double* d_grid_params, int32_t* d_cell_ptr,
+                                int32_t* d_cell_kp, int32_t* d_n_in_grid, void* stream);
+
+/* mvKeys rows as mcs_multiframe_concat_device leaves them (d_keys [cap], d_n = its d_total
+ * entry, NULL = cap) -> d_kp_xy [cap][2] (pt) and d_kp_octave [cap] (both nullable).  Its
+ * d_kp_to_cam and d_total are taken by the entries here as they are; its d_grid_pos subtracts
+ * in double, so the grid is built from the unpacked positions. */
+int mcs_track_unpack_keys_device(const mcs_keypoint* d_keys, const int32_t* d_n, int32_t cap,
+                                 float* d_kp_xy, int32_t* d_kp_octave, void* stream);
+
+/* Queries of rule 0 from the outputs of mcs_is_in_frustum_device ([n_points][n_cams]), one per
+ * (map point, camera) in that loop order: at (projX, projY), r = (viewCos > 0.998 ? 2.5 : 4.0),
+ * r *= th if th != 1.0, then r * scale[level]; levels (level - 1, level); descriptor index =
+ * the point.  d_skip [n_points] (nullable): the caller's snapshot of isBad() and of
+ * mnLastFrameSeen == the current frame (src/cTracking.cpp:961-1017).  A skipped point, a
+ * camera not in view or a level outside [0, n_levels) gives cam = -1 (an empty window).
+ * Out: d_q_xyr [nq][3], d_q_cam_lvl [nq][3], d_q_desc_idx [nq], nq = n_points * n_cams. */
+int mcs_track_queries_mappoints_device(const uint8_t* d_in_view, const double* d_proj,
+                                       const int32_t* d_level, const double* d_view_cos,
+                                       const uint8_t* d_skip, int32_t n_points, int32_t n_cams,
+                                       const double* d_scale, int32_t n_levels, double th,
+                                       double* d_q_xyr, int32_t* d_q_cam_lvl,
+                                       int32_t* d_q_desc_idx, void* stream);
+
+/* Queries of rule 1, one per keypoint slot of the last frame: d_pos [cap][3] the slot's map
+ * point in the world, d_valid [cap] = has a point, not bad, not mvbOutlier; projected with the
+ * current frame (pose, rig and level-0 mirror masks as mcs_is_in_frustum_device takes them)
+ * into the slot's own camera d_kp_cam [cap], through isPointInMirrorMask; r = th *
+ * scale[octave], levels (octave - 1, octave + 1); descriptor index = the slot.  d_n (nullable
+ * = cap): the last frame's keypoint count.  Invalid slots, slots past the count, a camera or
+ * octave out of range and projections outside the mask give cam = -1.  WorldToImg's angle is a
+ * correctly rounded atan: the projection has the reference's bits wherever the host libm's
+ * atan, which the reference calls, is correctly rounded too (all but about 2.5 arguments in
+ * ten thousand, and then they are one ulp apart).  It can differ in the last place from
+ * mcs_is_in_frustum_device's, which uses the device library's atan. */
+int mcs_track_queries_lastframe_device(const double* d_pose, const double* d_mc,
+                                       const double* d_cam, int32_t n_cams, const uint8_t* d_masks,
+                                       int32_t mask_w, int32_t mask_h, const double* d_pos,
+                                       const uint8_t* d_valid, const int32_t* d_kp_cam,
+                                       const int32_t* d_kp_octave, const int32_t* d_n, int32_t cap,
+                                       const double* d_scale, int32_t n_levels, double th,
+                                       double* d_q_xyr, int32_t* d_q_cam_lvl,
+                                       int32_t* d_q_desc_idx, void* stream);
+
+/* The frame searched (device pointers in the device entry).  n_kp = keypoint slots; the grid
+ * says which of them exist.  Grid counts and entries are clamped to n_kp when read. */
+typedef struct mcs_track_frame {
+  int32_t n_cams, n_kp, bytes;
+  const double* grid_params;     /* [n_cams][4] */
+  const int32_t* cell_ptr;       /* [n_cams*64*48 + 1] */
+  const int32_t* cell_kp;        /* [n_kp] */
+  const float* kp_xy;            /* [n_kp][2] */
+  const int32_t* kp_octave;      /* [n_kp] */
+  const uint8_t* desc;           /* [n_kp][bytes] */
+  const uint8_t* desc_mask;      /* nullable [n_kp][bytes] */
+} mcs_track_frame;
+
+/* The queries: query q reads row q_desc_idx[q] (NULL = q) of q_desc_src [n_src][bytes] (+
+ * q_mask_src, given exactly when the frame has masks); an index outside [0, n_src) is an
+ * empty window, like cam = -1. */
+typedef struct mcs_track_queries {
+  int32_t nq, n_src;
+  const double* q_xyr;           /* [nq][3] */
+  const int32_t* q_cam_lvl;      /* [nq][3] */
+  const int32_t* q_desc_idx;     /* nullable [nq] */
+  const uint8_t* q_desc_src;     /* [n_src][bytes] */
+  const uint8_t* q_mask_src;     /* nullable [n_src][bytes] */
+} mcs_track_queries;
+
+/* Count pass, scan, fill pass and the ordered selection of rule 0, 1 or 3 (rule 2:
+ * MCS_ERR_UNSUPPORTED), bit-equal to mcs_window_select over the same candidates.
+ * d_kp_assigned [n_kp] in/out; out: d_match [nq], d_kp_query [n_kp] (the query that took the
+ * keypoint in this call, or -1: what writes mvpMapPoints[bestIdx] = pMP), d_n_matches,
+ * d_status int64 [2] = {required candidate total, flags}.  When the total exceeds the
+ * workspace's cand_cap: d_match / d_kp_query all -1, d_n_matches 0, d_kp_assigned untouched,
+ * MCS_TRACK_OVERFLOW set; read the status when the results are read.
+ * The selection runs rounds in one launch, one workgroup per camera (no query crosses
+ * cameras): every unsettled query marks its unassigned candidates with an atomic (the lowest
+ * query wins); a query holding all its marks has no earlier unsettled query on any of its
+ * candidates, so it scans them in list order as the sequential loop would and settles; under
+ * rules 1 and 3 a match also stands as soon as no earlier unsettled query lists its best
+ * candidate (earlier queries only take keypoints away). */
+int mcs_track_search_device(mcs_track_workspace* ws, int32_t rule, const mcs_track_frame* frame,
+                            const mcs_track_queries* queries, int32_t th_high, double nnratio,
+                            uint8_t* d_kp_assigned, int32_t* d_match, int32_t* d_kp_query,
+                            int32_t* d_n_matches, int64_t* d_status, void* stream);
+
+/* The selection alone over the candidate lists the workspace holds from its last search with
+ * the same queries (d_q_cam_lvl [nq][3], d_kp_octave [n_kp]).  d_status: the total and the
+ * overflow flag as the search left them; the rounds field is set to this call's. */
+int mcs_track_select_device(mcs_track_workspace* ws, int32_t rule, int32_t nq,
+                            const int32_t* d_q_cam_lvl, const int32_t* d_kp_octave, int32_t n_kp,
+                            int32_t n_cams, int32_t th_high, double nnratio,
+                            uint8_t* d_kp_assigned, int32_t* d_match, int32_t* d_kp_query,
+                            int32_t* d_n_matches, int64_t* d_status, void* stream);
+
+/* Host-buffer entries for the reference's call sites: upload, run the device form on `device`
+ * and download (MCS_ERR_NO_DEVICE without a GPU, no CPU fallback).  mcs_track_search builds
+ * the grid on the device and sizes the candidate lists itself; kp_assigned and kp_query may
+ * be NULL.  The two query entries run the kernels above on host arrays. */
+int mcs_track_search(int32_t device, int32_t rule, const mcs_window_frame* frame,
+                     const mcs_track_queries* queries, int32_t th_high, double nnratio,
+                     uint8_t* kp_assigned, int32_t* match, int32_t* kp_query, int32_t* n_matches);
+int mcs_track_queries_mappoints(int32_t device, const uint8_t* in_view, const double* proj,
+                                const int32_t* level, const double* view_cos, const uint8_t* skip,
+                                int32_t n_points, int32_t n_cams, const double* scale,
+                                int32_t n_levels, double th, double* q_xyr, int32_t* q_cam_lvl,
+                                int32_t* q_desc_idx);
+int mcs_track_queries_lastframe(int32_t device, const double* pose, const double* mc,
+                                const double* cam, int32_t n_cams, const uint8_t* masks,
+                                int32_t mask_w, int32_t mask_h, const double* pos,
+                                const uint8_t* valid, const int32_t* kp_cam,
+                                const int32_t* kp_octave, int32_t n, const double* scale,
+                                int32_t n_levels, double th, double* q_xyr, int32_t* q_cam_lvl,
+                                int32_t* q_desc_idx);
 
 /* ---- SearchByBoW: relocalisation and loop detection -------------------------------------
  *   int SearchByBoW(cMultiKeyFrame* pKF, cMultiFrame& F, vpMapPointMatches)

@@ -1,14 +1,15 @@
-// Device functions shared by frame.hip, window.hip, hamming.hip, fuse.hip, sim3_match.hip and
-// sim3_solver.hip: the
+// Device functions shared by frame.hip, window.hip, track_match.hip, hamming.hip, fuse.hip,
+// sim3_match.hip and sim3_solver.hip: the
 // omni projection (cayley2rot, M_t M_c, invMat, WorldToCamHom_fast / WorldToImg, ImgToWorld,
 // isPointInMirrorMask), the predicted pyramid level, the window
 // cell range of GetFeaturesInArea, the descriptor distance of a window candidate, the
-// wave-per-query window walk and CheckDistEpipolarLine.  One definition each, so every entry that
-// uses them gives the same bits.
+// wave-per-query candidate and best-candidate walks and CheckDistEpipolarLine.  One definition
+// each, so every entry that uses them gives the same bits.
 // Translation units that include this are compiled with -ffp-contract=off; double ops are spelled
 // with _rn intrinsics where an FMA could otherwise be formed.
 #pragma once
 #include "common.hpp"
+#include "atan_cr.hpp"
 #include "../../include/mcs_extractor.h"
 #include "../../include/mcs_matcher.h"
 
@@ -84,12 +85,16 @@ __device__ inline void mtmc44(const double* Mt, const double* Mc, double* R, dou
     }
 }
 
-// WorldToImg (cam_model_omni.cpp:147-163); cam = c d e u0 v0 invP[12]
+// WorldToImg (cam_model_omni.cpp:147-163); cam = c d e u0 v0 invP[12].  CR: theta from the
+// correctly rounded atan_cr (the host libm's result wherever the libm rounds correctly)
+// instead of the device library's atan, for entries whose projection is held to the
+// reference's bits; the default keeps every existing entry's bits.
+template <bool CR = false>
 __device__ __forceinline__ void world_to_img(const double* cam, double x, double y, double z,
                                              double& u, double& v) {
   double norm = __dsqrt_rn(__dadd_rn(__dmul_rn(x, x), __dmul_rn(y, y)));
   if (norm == 0.0) norm = 1e-14;
-  const double theta = atan(__ddiv_rn(-z, norm));
+  const double theta = CR ? atan_cr(__ddiv_rn(-z, norm)) : atan(__ddiv_rn(-z, norm));
   const double rho = horner_n(cam + 5, 12, theta);
   const double uu = __dmul_rn(__ddiv_rn(x, norm), rho), vv = __dmul_rn(__ddiv_rn(y, norm), rho);
   u = __dadd_rn(__dadd_rn(__dmul_rn(uu, cam[0]), __dmul_rn(vv, cam[1])), cam[3]);
@@ -97,6 +102,7 @@ __device__ __forceinline__ void world_to_img(const double* cam, double x, double
 }
 
 // WorldToCamHom_fast (cam_system_omni.cpp:92-112): invMat(M_t M_c) * [X 1], then WorldToImg
+template <bool CR = false>
 __device__ inline void world_to_cam_img(const double* R, const double* t, const double* cam,
                                         const double* X, double& u, double& v) {
   double ti[3];   // invMat: R' = R^T, t' = -R' t (cConverter.cpp:31-44)
@@ -114,7 +120,7 @@ __device__ inline void world_to_cam_img(const double* R, const double* t, const 
     s = __dadd_rn(s, __dmul_rn(ti[i], 1.0));
     Xc[i] = s;
   }
-  world_to_img(cam, Xc[0], Xc[1], Xc[2], u, v);
+  world_to_img<CR>(cam, Xc[0], Xc[1], Xc[2], u, v);
 }
 
 // invMat (cConverter.cpp:31-44) of a row-major 4x4: R' = R^T, t' = -R' * t
@@ -191,6 +197,89 @@ __device__ __forceinline__ int ham(const uint8_t* q, const uint8_t* t, const uin
     d += __popc(x & ma[w]) + __popc(x & mb[w]);
   }
   return d / 2;
+}
+
+// One frame's keypoints and feature grid as the candidate walk reads them.
+struct CandFrame {
+  const int32_t* cell_ptr; const int32_t* cell_kp; const double* gp; int n_cams;
+  const float* kp_xy; const int32_t* kp_oct; const uint8_t* kp_desc; const uint8_t* kp_mask;
+  int bytes;
+};
+
+// GetFeaturesInArea + the distance of every candidate, one wave per query (k_window and
+// k_track_window).  The window's cells are taken 64 at a time, one per lane in the
+// reference's loop order (ix outer, iy inner); a wave prefix sum over the cell sizes flattens
+// their keypoints (insertion order within a cell), so a step costs two dependent loads for 64
+// cells instead of a chain per cell.  Candidates passing the level and |dx|, |dy| <= r tests
+// are compacted by ballot rank, which keeps the reference's order.  Returns the count.
+// COUNT: count only; else write (keypoint, distance) from `base`.  CLAMP: the grid is device
+// data nobody checked: cell ranges and entries are clamped to n_kp (as walk_best does) and
+// nothing is written at or past `end`.
+template <bool COUNT, bool CLAMP>
+__device__ __forceinline__ int window_candidates(const CandFrame& a, int lane, double x, double y,
+                                                 double r, int cam, int minL, int maxL,
+                                                 const uint8_t* qd, const uint8_t* qm, int n_kp,
+                                                 int base, int end, int32_t* cand_kp,
+                                                 int32_t* cand_dist) {
+  int cnt = 0;
+  int x0, x1, y0, y1;
+  if (cam >= 0 && cam < a.n_cams && cell_range(a.gp + 4 * cam, x, y, r, &x0, &x1, &y0, &y1)) {
+    const bool check = !(minL == -1 && maxL == -1);
+    const bool same = check && (minL == maxL);
+    const int ncy = y1 - y0 + 1, ncell = (x1 - x0 + 1) * ncy;
+    for (int cb = 0; cb < ncell; cb += 64) {
+      const int ci = cb + lane;
+      int start = 0, len = 0;
+      if (ci < ncell) {
+        const int cell = (cam * kCols + x0 + ci / ncy) * kRows + y0 + ci % ncy;
+        start = a.cell_ptr[cell];
+        len = a.cell_ptr[cell + 1] - start;
+        if (CLAMP) {
+          start = min(max(start, 0), n_kp);
+          len = min(max(len, 0), n_kp - start);
+        }
+      }
+      const int incl = dev::wave_incl_scan(len);
+      const int off = incl - len;
+      const int tot = __shfl(incl, 63);
+      for (int e0 = 0; e0 < tot; e0 += 64) {
+        const int e = e0 + lane;
+        // owning cell = the last lane whose offset is <= e (an empty cell shares its offset
+        // with the next cell, lanes past the window hold tot)
+        int o = 0;
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1)
+          if (__shfl(off, o + s) <= e) o += s;
+        const int so = __shfl(start, o), oo = __shfl(off, o);
+        bool ok = false;
+        int k = 0;
+        if (e < tot) {
+          k = a.cell_kp[so + (e - oo)];
+          ok = !CLAMP || (k >= 0 && k < n_kp);
+          if (ok) {
+            const int oc = a.kp_oct[k];
+            if (check && !same) ok = !(oc < minL || oc > maxL);
+            else if (same) ok = (oc == minL);
+          }
+          if (ok) {
+            const double dx = (double)a.kp_xy[2 * k] - x, dy = (double)a.kp_xy[2 * k + 1] - y;
+            ok = !(fabs(dx) > r || fabs(dy) > r);
+          }
+        }
+        const uint64_t bal = __ballot(ok);
+        if (!COUNT && ok) {
+          const int pos = base + cnt + __popcll(bal & dev::lanemask_lt());
+          if (!CLAMP || pos < end) {
+            cand_kp[pos] = k;
+            cand_dist[pos] = ham(qd, a.kp_desc + (int64_t)k * a.bytes, qm,
+                                 a.kp_mask ? a.kp_mask + (int64_t)k * a.bytes : nullptr, a.bytes);
+          }
+        }
+        cnt += __popcll(bal);
+      }
+    }
+  }
+  return cnt;
 }
 
 // The window walk of the wave-per-query searches (k_fuse, k_sim3_search), after cell_range said

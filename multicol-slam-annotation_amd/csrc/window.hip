@@ -36,11 +36,7 @@ struct SearchArgs {
   int32_t* cand_ptr; int32_t* cand_kp; int32_t* cand_dist;
 };
 
-// One wave per query.  The window's cells are taken 64 at a time, one per lane in the
-// reference's loop order (ix outer, iy inner); a wave prefix sum over the cell sizes flattens
-// their keypoints (insertion order within a cell), so a step costs two dependent loads for 64
-// cells instead of a chain per cell.  Candidates passing the level and |dx|, |dy| <= r tests
-// are compacted by ballot rank, which keeps the reference's order.
+// One wave per query: win::window_candidates (proj_window.hpp), the grid taken as given.
 // COUNT: count only; else write (keypoint, distance) from cand_ptr[q].
 template <bool COUNT>
 __global__ __launch_bounds__(256) void k_window(SearchArgs a) {
@@ -49,59 +45,13 @@ __global__ __launch_bounds__(256) void k_window(SearchArgs a) {
   if (q >= a.nq) return;
   const double x = a.q_xyr[3 * q], y = a.q_xyr[3 * q + 1], r = a.q_xyr[3 * q + 2];
   const int cam = a.q_cl[3 * q], minL = a.q_cl[3 * q + 1], maxL = a.q_cl[3 * q + 2];
-  int cnt = 0;
-  int x0, x1, y0, y1;
-  if (cam >= 0 && cam < a.n_cams && cell_range(a.gp + 4 * cam, x, y, r, &x0, &x1, &y0, &y1)) {
-    const bool check = !(minL == -1 && maxL == -1);
-    const bool same = check && (minL == maxL);
-    const uint8_t* qd = a.q_desc + (int64_t)q * a.bytes;
-    const uint8_t* qm = a.q_mask ? a.q_mask + (int64_t)q * a.bytes : nullptr;
-    const int base = COUNT ? 0 : a.cand_ptr[q];
-    const int ncy = y1 - y0 + 1, ncell = (x1 - x0 + 1) * ncy;
-    for (int cb = 0; cb < ncell; cb += 64) {
-      const int ci = cb + lane;
-      int start = 0, len = 0;
-      if (ci < ncell) {
-        const int cell = (cam * kCols + x0 + ci / ncy) * kRows + y0 + ci % ncy;
-        start = a.cell_ptr[cell];
-        len = a.cell_ptr[cell + 1] - start;
-      }
-      const int incl = dev::wave_incl_scan(len);
-      const int off = incl - len;
-      const int tot = __shfl(incl, 63);
-      for (int e0 = 0; e0 < tot; e0 += 64) {
-        const int e = e0 + lane;
-        // owning cell = the last lane whose offset is <= e (an empty cell shares its offset
-        // with the next cell, lanes past the window hold tot)
-        int o = 0;
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1)
-          if (__shfl(off, o + s) <= e) o += s;
-        const int so = __shfl(start, o), oo = __shfl(off, o);
-        bool ok = false;
-        int k = 0;
-        if (e < tot) {
-          k = a.cell_kp[so + (e - oo)];
-          const int oc = a.kp_oct[k];
-          ok = true;
-          if (check && !same) ok = !(oc < minL || oc > maxL);
-          else if (same) ok = (oc == minL);
-          if (ok) {
-            const double dx = (double)a.kp_xy[2 * k] - x, dy = (double)a.kp_xy[2 * k + 1] - y;
-            ok = !(fabs(dx) > r || fabs(dy) > r);
-          }
-        }
-        const uint64_t bal = __ballot(ok);
-        if (!COUNT && ok) {
-          const int pos = base + cnt + __popcll(bal & dev::lanemask_lt());
-          a.cand_kp[pos] = k;
-          a.cand_dist[pos] = ham(qd, a.kp_desc + (int64_t)k * a.bytes, qm,
-                                 a.kp_mask ? a.kp_mask + (int64_t)k * a.bytes : nullptr, a.bytes);
-        }
-        cnt += __popcll(bal);
-      }
-    }
-  }
+  const CandFrame f{a.cell_ptr, a.cell_kp, a.gp, a.n_cams, a.kp_xy, a.kp_oct, a.kp_desc, a.kp_mask,
+                    a.bytes};
+  const uint8_t* qd = a.q_desc + (int64_t)q * a.bytes;
+  const uint8_t* qm = a.q_mask ? a.q_mask + (int64_t)q * a.bytes : nullptr;
+  const int cnt = window_candidates<COUNT, false>(f, lane, x, y, r, cam, minL, maxL, qd, qm, 0,
+                                                  COUNT ? 0 : a.cand_ptr[q], 0, a.cand_kp,
+                                                  a.cand_dist);
   if (COUNT && lane == 0) a.cand_ptr[q + 1] = cnt;
 }
 

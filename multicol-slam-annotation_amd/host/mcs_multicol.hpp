@@ -13,6 +13,9 @@
 //                                                     mcs::GlobalBA::run(map, poseOnly, pbStopFlag)
 //   cOptimizer::PoseOptimization (cOptimizer.h:67-69) mcs::PoseOptimizer::run(frame, inliers,
 //                                                                        huberMultiplier)
+//   cORBmatcher::SearchByProjection(F, vpMapPoints, th) / (CurrentFrame, LastFrame, th)
+//     (src/cORBmatcher.cpp:67-166, :1991-2123)       mcs::SearchByProjection(rig, F, mapPoints, th, ...) /
+//                                                     mcs::SearchByProjection(rig, mc6, Current, Last, ...)
 //   cLocalMapping::CreateNewMapPoints (src/cLocalMapping.cpp:224-386)
 //                                                     mcs::CreateNewMapPoints(rig, cur, neighbours, ...)
 //   cMultiKeyFrameDatabase (src/cMultiKeyFrameDatabase.cpp:43-340)
@@ -520,6 +523,94 @@ inline std::vector<int> Fuse(int rule, const FuseRig& rig, const std::vector<con
     t0 = next;
   }
   return n_fused;
+}
+
+// cORBmatcher::SearchByProjection(F, vpMapPoints, th) (src/cORBmatcher.cpp:67-166) at
+// cTracking::SearchReferencePointsInFrustum (src/cTracking.cpp:961-1017) and
+// SearchByProjection(CurrentFrame, LastFrame, th) (:1991-2123) at TrackWithMotionModel, on the
+// host-buffer entries of the device form (mcs_track_queries_*, mcs_track_search): queries, grid,
+// candidates and the ordered selection all run on the device.  A frame is a FuseKeyFrame (its
+// keypoints and descriptors) with its mvpMapPoints as ids.
+struct TrackFrame {
+  const FuseKeyFrame* keys = nullptr;
+  std::vector<int32_t> map_point;   // [n] mvpMapPoints as map-point ids, -1 = NULL (in / out)
+  double pose[6] = {0, 0, 0, 0, 0, 0};   // M_t in its minimal form: Cayley rotation, translation
+};
+struct TrackMapPoints {             // vpMapPoints after isInFrustum ran on each of them
+  std::vector<int32_t> mp;          // [n] map-point id
+  std::vector<uint8_t> skip;        // [n] isBad(), or mnLastFrameSeen == the frame (already matched)
+  std::vector<uint8_t> in_view;     // [n][n_cams] mbTrackInView
+  std::vector<double> proj;         // [n][n_cams][2] mTrackProjX / Y
+  std::vector<int32_t> level;       // [n][n_cams] mnTrackScaleLevel
+  std::vector<double> view_cos;     // [n][n_cams] mTrackViewCos
+  std::vector<uint8_t> desc, mask;  // [n][bytes] GetDescriptor (+ mask)
+};
+struct TrackLastPoints {            // the last frame's slots as :2006-2018 read them
+  std::vector<uint8_t> valid;       // [n] has a point, not isBad(), not mvbOutlier
+  std::vector<double> pos;          // [n][3] GetWorldPos (any value where not valid)
+};
+
+namespace detail {
+inline mcs_window_frame track_window_frame(const FuseRig& rig, const FuseKeyFrame& k, int bytes) {
+  return mcs_window_frame{rig.n_cams, (int32_t)k.kp_octave.size(), bytes, rig.grid_params.data(),
+                          k.kp_xy.data(), k.kp_cam.data(), k.kp_octave.data(), k.desc.data(),
+                          k.mask.empty() ? nullptr : k.mask.data()};
+}
+// runs the search and writes mvpMapPoints[bestIdx] = the query's point; id_of(query) names it
+template <class IdOf>
+inline int track_search(int device, int rule, const FuseRig& rig, TrackFrame& F, int bytes,
+                        const std::vector<double>& q_xyr, const std::vector<int32_t>& q_cl,
+                        const std::vector<int32_t>& q_idx, const std::vector<uint8_t>& src,
+                        const std::vector<uint8_t>& src_mask, int th_high, double nnratio, IdOf id_of) {
+  const int n = (int)F.keys->kp_octave.size(), nq = (int)q_idx.size();
+  if ((int)F.map_point.size() != n) throw std::runtime_error("SearchByProjection: map_point size");
+  const mcs_window_frame wf = track_window_frame(rig, *F.keys, bytes);
+  const mcs_track_queries q{nq, (int32_t)(src.size() / (size_t)bytes), q_xyr.data(), q_cl.data(), q_idx.data(),
+                            src.data(), src_mask.empty() ? nullptr : src_mask.data()};
+  std::vector<uint8_t> assigned((size_t)std::max(1, n), 0);
+  for (int i = 0; i < n; i++) assigned[i] = F.map_point[i] >= 0;
+  std::vector<int32_t> match((size_t)std::max(1, nq)), kp_query((size_t)std::max(1, n));
+  int32_t nm = 0;
+  check(mcs_track_search(device, rule, &wf, &q, th_high, nnratio, assigned.data(), match.data(), kp_query.data(),
+                         &nm), "mcs_track_search");
+  for (int i = 0; i < n; i++)
+    if (kp_query[i] >= 0) F.map_point[i] = id_of(kp_query[i]);
+  return nm;
+}
+}  // namespace detail
+
+// th_high = the matcher's TH_HIGH_ (3 * bytes, or floor(1.5 * bytes) with masks), nnratio its
+// mfNNratio.  Returns nmatches; F.map_point receives the matched points.
+inline int SearchByProjection(const FuseRig& rig, TrackFrame& F, const TrackMapPoints& mps, double th, int bytes,
+                              int th_high, double nnratio, int device = 0) {
+  const int n = (int)mps.mp.size(), C = rig.n_cams;
+  const size_t nq = (size_t)n * C;
+  std::vector<double> q_xyr(3 * nq + 1);
+  std::vector<int32_t> q_cl(3 * nq + 1), q_idx(nq);
+  check(mcs_track_queries_mappoints(device, mps.in_view.data(), mps.proj.data(), mps.level.data(),
+                                    mps.view_cos.data(), mps.skip.empty() ? nullptr : mps.skip.data(), n, C,
+                                    rig.scale.data(), (int32_t)rig.scale.size(), th, q_xyr.data(), q_cl.data(),
+                                    q_idx.data()), "mcs_track_queries_mappoints");
+  return detail::track_search(device, 0, rig, F, bytes, q_xyr, q_cl, q_idx, mps.desc, mps.mask, th_high, nnratio,
+                              [&](int q) { return mps.mp[(size_t)q / C]; });
+}
+
+// mc6 [n_cams][6]: M_c of every camera in the same minimal form as the pose.  last_mp = the last
+// frame's mvpMapPoints ids; Current.map_point receives them.
+inline int SearchByProjection(const FuseRig& rig, const std::vector<double>& mc6, TrackFrame& Current,
+                              const TrackFrame& Last, const TrackLastPoints& last_pts, double th, int bytes,
+                              int th_high, double nnratio, int device = 0) {
+  const FuseKeyFrame& L = *Last.keys;
+  const int n = (int)L.kp_octave.size();
+  std::vector<double> q_xyr(3 * (size_t)n + 1);
+  std::vector<int32_t> q_cl(3 * (size_t)n + 1), q_idx((size_t)n);
+  check(mcs_track_queries_lastframe(device, Current.pose, mc6.data(), rig.cam.data(), rig.n_cams, rig.mirror.data(),
+                                    rig.mirror_w, rig.mirror_h, last_pts.pos.data(), last_pts.valid.data(),
+                                    L.kp_cam.data(), L.kp_octave.data(), n, rig.scale.data(),
+                                    (int32_t)rig.scale.size(), th, q_xyr.data(), q_cl.data(), q_idx.data()),
+        "mcs_track_queries_lastframe");
+  return detail::track_search(device, 1, rig, Current, bytes, q_xyr, q_cl, q_idx, L.desc, L.mask, th_high, nnratio,
+                              [&](int q) { return Last.map_point[(size_t)q]; });
 }
 
 // cORBmatcher::SearchBySim3 (src/cORBmatcher.cpp:1721-1988) at cLoopClosing::ComputeSim3

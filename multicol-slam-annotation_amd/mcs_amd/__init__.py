@@ -155,6 +155,23 @@ SIGNATURES = {
     "mcs_window_search_device": (ctypes.c_int, [_P, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P]),
     "mcs_window_select": (ctypes.c_int, [_I32, _I32, _P, _P, _P, _P, _I32, _I32, ctypes.c_double, _P, _P, _P]),
     "mcs_window_match": (ctypes.c_int, [_I32, _I32, _P, _I32, _P, _P, _P, _P, _I32, ctypes.c_double, _P, _P, _P]),
+    # tracking matchers on the device (include/mcs_matcher.h; wrappers in mcs_amd/track_match.py)
+    "mcs_track_workspace_create": (ctypes.c_int, [_I32, _I32, _I32, _I64, _P]),
+    "mcs_track_workspace_destroy": (None, [_P]),
+    "mcs_frame_grid_build_device": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
+    "mcs_track_unpack_keys_device": (ctypes.c_int, [_P, _P, _I32, _P, _P, _P]),
+    "mcs_track_queries_mappoints_device": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _P, _I32,
+                                                          ctypes.c_double, _P, _P, _P, _P]),
+    "mcs_track_queries_lastframe_device": (ctypes.c_int, [_P, _P, _P, _I32, _P, _I32, _I32, _P, _P, _P, _P,
+                                                          _P, _I32, _P, _I32, ctypes.c_double, _P, _P, _P, _P]),
+    "mcs_track_search_device": (ctypes.c_int, [_P, _I32, _P, _P, _I32, ctypes.c_double, _P, _P, _P, _P, _P, _P]),
+    "mcs_track_select_device": (ctypes.c_int, [_P, _I32, _I32, _P, _P, _I32, _I32, _I32, ctypes.c_double,
+                                               _P, _P, _P, _P, _P, _P]),
+    "mcs_track_search": (ctypes.c_int, [_I32, _I32, _P, _P, _I32, ctypes.c_double, _P, _P, _P, _P]),
+    "mcs_track_queries_mappoints": (ctypes.c_int, [_I32, _P, _P, _P, _P, _P, _I32, _I32, _P, _I32,
+                                                   ctypes.c_double, _P, _P, _P]),
+    "mcs_track_queries_lastframe": (ctypes.c_int, [_I32, _P, _P, _P, _I32, _P, _I32, _I32, _P, _P, _P, _P,
+                                                   _I32, _P, _I32, ctypes.c_double, _P, _P, _P]),
     # SearchByBoW (include/mcs_matcher.h; wrappers in mcs_amd/bow_match.py)
     "mcs_bow_workspace_create": (ctypes.c_int, [_I32, _I32, _I32, _P]),
     "mcs_bow_workspace_destroy": (None, [_P]),
