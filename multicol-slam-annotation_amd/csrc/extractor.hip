@@ -59,14 +59,21 @@ struct mcs_extractor {
   uint8_t* d_mask_single = nullptr;
   // k_pyr_rows unit tables (pyr_units.hpp), one per batch-size class and kind, built on first
   // use: full = every pixel (no registered mask, the single-call path, dBRIEF / mdBRIEF, whose
-  // distorted pattern has no fixed reach); masked = per registered mask, from its need set
+  // distorted pattern has no fixed reach); masked = per registered mask, from its need set.
+  // The units of a table are packed into waves for groups of G frames of one mask
+  // (pack_pyr_units): G == 1 is one strip per wave.
   struct PyrTable {
-    int fclass = 0; bool masked = false;
-    mcs::PyrUnit* d_units = nullptr; int64_t mstride = 0;
+    int fclass = 0; bool masked = false; int G = 1;
+    mcs::PyrWave* d_waves = nullptr; int64_t mstride = 0;
     int32_t off[mcs::kMaxLevels] = {}, n[mcs::kMaxLevels] = {};
   };
   std::vector<PyrTable> pyr_tabs;
   std::vector<mcs::PyrNeed> pyr_need;   // per registered mask
+  // which frames of the batch share a group (k_pyr_groups, rebuilt by every masked batch):
+  // [group_cap * G] frames and [group_cap] mask indices
+  int32_t* d_group_frames = nullptr; int32_t* d_group_mask = nullptr; int64_t group_cap = 0;
+  // k_pyr_groups' counters where the masks outnumber its LDS ones: [5 * n_masks]
+  int32_t* d_group_scratch = nullptr; int64_t group_scratch_cap = 0;
   // single-frame staging
   uint8_t* d_in = nullptr;
   mcs_keypoint* d_kps = nullptr; uint8_t* d_desc = nullptr; int32_t* d_count = nullptr;
@@ -99,35 +106,37 @@ static void fill_level_ptrs(const Plan& pl, LevelPtrs& lp) {
 
 // The unit table for batches of F frames (built and uploaded on the first batch of a size
 // class; F >= kPyrFrameClasses share one)
-static int pyr_table(mcs_extractor* h, int F, bool masked, const mcs_extractor::PyrTable** out) {
+static int pyr_table(mcs_extractor* h, int F, bool masked, int G, const mcs_extractor::PyrTable** out) {
   const int fc = pyr_frame_class(F);
   for (const auto& t : h->pyr_tabs)
-    if (t.fclass == fc && t.masked == masked) { *out = &t; return MCS_OK; }
+    if (t.fclass == fc && t.masked == masked && t.G == G) { *out = &t; return MCS_OK; }
   const Plan& pl = h->plan;
   const int nm = masked ? (int)h->pyr_need.size() : 1;
-  std::vector<std::vector<PyrUnit>> lists((size_t)nm * kMaxLevels);
+  std::vector<std::vector<PyrWave>> lists((size_t)nm * kMaxLevels);
   mcs_extractor::PyrTable t;
-  t.fclass = fc; t.masked = masked;
+  t.fclass = fc; t.masked = masked; t.G = G;
   for (int m = 0; m < nm; m++) {
     std::vector<PyrUnit> lv[kMaxLevels];
+    std::vector<PyrWave> wv[kMaxLevels];
     build_pyr_units(pl, masked ? &h->pyr_need[m] : nullptr, fc, lv);
+    pack_pyr_units(pl, lv, G, wv);
     for (int l = 0; l < pl.nlevels; l++) {
-      t.n[l] = std::max(t.n[l], (int32_t)lv[l].size());
-      lists[(size_t)m * kMaxLevels + l].swap(lv[l]);
+      t.n[l] = std::max(t.n[l], (int32_t)wv[l].size());
+      lists[(size_t)m * kMaxLevels + l].swap(wv[l]);
     }
   }
   int64_t stride = 0;
   for (int l = 0; l < pl.nlevels; l++) { t.off[l] = (int32_t)stride; stride += t.n[l]; }
   stride = std::max<int64_t>(stride, 1);
-  std::vector<PyrUnit> all((size_t)nm * stride, PyrUnit{0, 0, 0, 0});   // pads: no rows
+  std::vector<PyrWave> all((size_t)nm * stride, PyrWave{0, 0, 0, 0, {{0, 0}, {0, 0}}});   // pads: no rows
   for (int m = 0; m < nm; m++)
     for (int l = 0; l < pl.nlevels; l++) {
       const auto& v = lists[(size_t)m * kMaxLevels + l];
       std::copy(v.begin(), v.end(), all.begin() + (size_t)m * stride + t.off[l]);
     }
-  int rc = dalloc(&t.d_units, all.size());
+  int rc = dalloc(&t.d_waves, all.size());
   if (rc) return rc;
-  MCS_HIP_CHECK(hipMemcpy(t.d_units, all.data(), all.size() * sizeof(PyrUnit), hipMemcpyHostToDevice));
+  MCS_HIP_CHECK(hipMemcpy(t.d_waves, all.data(), all.size() * sizeof(PyrWave), hipMemcpyHostToDevice));
   t.mstride = nm > 1 ? stride : 0;
   h->pyr_tabs.push_back(t);
   *out = &h->pyr_tabs.back();
@@ -148,7 +157,9 @@ static int run_batch(mcs_extractor* h, const uint8_t* d_images, int F, const uin
   const int nl = pl.nlevels;
   const int64_t img0_fs = (int64_t)pl.W * pl.H;
   // the FAST waves of level 0 are packed for dword-aligned rows when W is a multiple of 4
-  // (fast_run_lanes: no spare lane for a row's byte offset)
+  // (fast_run_lanes: no spare lane for a row's byte offset), and so are the pyramid's two-run
+  // waves of level 1 and the level-0 blur (pack_pyr_units counts their staged dwords from a
+  // byte shift of 0 where the pitch is a multiple of 4)
   if (pl.W % 4 == 0 && ((uintptr_t)d_images & 3) != 0) {
     set_error("images must be 4-byte aligned when the width is a multiple of 4");
     return MCS_ERR_ARG;
@@ -157,9 +168,39 @@ static int run_batch(mcs_extractor* h, const uint8_t* d_images, int F, const uin
   const bool per_mask = mask_pyr && mask_pyr == h->d_mask_pyr && h->d_munits;
   const bool orb = !pl.p.learn_masks && !pl.p.do_dbrief;
   const mcs_extractor::PyrTable* pt = nullptr;
+  // Frames of one mask go G to a group, whose strips share waves (pack_pyr_units).  A lane
+  // reaches its frame by a 32-bit offset from the wave's first one: one strip per wave where
+  // a batch is longer than that.
+  const int64_t max_fs = std::max({img0_fs, pl.pyr_frame_bytes, pl.img_frame_bytes});
+  const int G = (int64_t)F * max_fs < (int64_t)1 << 32 ? std::min(kPyrGroup, pyr_frame_class(F)) : 1;
   {
-    const int rc = pyr_table(h, F, per_mask && orb && !h->pyr_need.empty(), &pt);
+    const int rc = pyr_table(h, F, per_mask && orb && !h->pyr_need.empty(), G, &pt);
     if (rc) return rc;
+  }
+  // with a table per mask the groups follow the batch's mask indices, in any order: sorted on
+  // the device at the head of the batch.  Otherwise a group is G consecutive frames.
+  const bool sorted = pt->mstride && d_mask_index;
+  const int ngroups = sorted ? pyr_groups_max(F, G, h->n_masks) : (F + G - 1) / G;
+  if (sorted) {
+    if (ngroups > h->group_cap) {
+      if (h->d_group_frames) MCS_HIP_CHECK(hipFree(h->d_group_frames));
+      if (h->d_group_mask) MCS_HIP_CHECK(hipFree(h->d_group_mask));
+      h->d_group_frames = h->d_group_mask = nullptr;
+      h->group_cap = 0;
+      int rc = dalloc(&h->d_group_frames, (size_t)ngroups * kPyrGroup);
+      if (!rc) rc = dalloc(&h->d_group_mask, (size_t)ngroups);
+      if (rc) return rc;
+      h->group_cap = ngroups;
+    }
+    const int64_t scratch = h->n_masks > kPyrGroupMasks ? 5 * (int64_t)h->n_masks : 0;
+    if (scratch > h->group_scratch_cap) {
+      if (h->d_group_scratch) MCS_HIP_CHECK(hipFree(h->d_group_scratch));
+      h->d_group_scratch = nullptr;
+      h->group_scratch_cap = 0;
+      const int rc = dalloc(&h->d_group_scratch, (size_t)scratch);
+      if (rc) return rc;
+      h->group_scratch_cap = scratch;
+    }
   }
   auto pyr_args = [&](int l) {
     PyrArgs a;
@@ -182,8 +223,10 @@ static int run_batch(mcs_extractor* h, const uint8_t* d_images, int F, const uin
     a.dw = D.w; a.dh = D.h;
     pyr_strips(D.w, D.h, F, a);
     a.nframes = F;
-    a.units = pt->d_units + pt->off[l]; a.nunits = pt->n[l]; a.unit_mstride = pt->mstride;
-    a.mask_index = pt->mstride ? d_mask_index : nullptr; a.nmasks = h->n_masks;
+    a.waves = pt->d_waves + pt->off[l]; a.nwaves = pt->n[l]; a.wave_mstride = pt->mstride;
+    a.group_frames = sorted ? h->d_group_frames : nullptr;
+    a.group_mask = sorted ? h->d_group_mask : nullptr;
+    a.ngroups = ngroups; a.gsize = G;
     return a;
   };
   // K2 arguments (row-streaming FAST; one launch per level, units of a level are contiguous)
@@ -217,6 +260,9 @@ static int run_batch(mcs_extractor* h, const uint8_t* d_images, int F, const uin
     MCS_HIP_CHECK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
   }
   stage_mark(h, 0, st);
+  if (sorted)   // before the fork: both streams read the groups
+    launch_pyr_groups(d_mask_index, F, h->n_masks, G, h->d_group_frames, h->d_group_mask,
+                      h->d_group_scratch, st);
   if (use_side) {
     MCS_HIP_CHECK(hipEventRecord(h->ev_fork, st));
     MCS_HIP_CHECK(hipStreamWaitEvent(h->side, h->ev_fork, 0));
@@ -367,14 +413,15 @@ void mcs_extractor_destroy(mcs_extractor* h) {
   void* ptrs[] = {h->d_xofs, h->d_alpha, h->d_yofs, h->d_beta, h->d_cells, h->d_units, h->d_pyr, h->d_blur,
                   h->d_slots, h->d_cell_counts, h->d_cand, h->d_cnode, h->d_sel, h->d_sel_count,
                   h->d_mask_pyr, h->d_munits, h->d_mask_single, h->d_in,
-                  h->d_kps, h->d_desc, h->d_count, h->d_dmask, h->d_cams};
+                  h->d_kps, h->d_desc, h->d_count, h->d_dmask, h->d_cams,
+                  h->d_group_frames, h->d_group_mask, h->d_group_scratch};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (h->side) (void)hipStreamDestroy(h->side);
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
   if (h->ev_join) (void)hipEventDestroy(h->ev_join);
   for (auto& t : h->pyr_tabs)
-    if (t.d_units) (void)hipFree(t.d_units);
+    if (t.d_waves) (void)hipFree(t.d_waves);
   if (h->ev) {
     for (int i = 0; i < mcs_extractor::kRing * (MCS_EXTRACTOR_NSTAGES + 1); i++)
       (void)hipEventDestroy(h->ev[i]);
@@ -437,7 +484,7 @@ int mcs_extractor_set_masks_device(mcs_extractor* h, const uint8_t* d_masks, int
   h->munit_stride = 0;
   // the per-mask pyramid tables go with the masks (hipFree waits for the kernels reading them)
   for (auto it = h->pyr_tabs.begin(); it != h->pyr_tabs.end();) {
-    if (it->masked) { MCS_HIP_CHECK(hipFree(it->d_units)); it = h->pyr_tabs.erase(it); }
+    if (it->masked) { MCS_HIP_CHECK(hipFree(it->d_waves)); it = h->pyr_tabs.erase(it); }
     else ++it;
   }
   h->pyr_need.clear();

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "extractor_plan.hpp"
+#include "pyr_groups.hpp"
 #include "pyr_units.hpp"
 
 namespace mcs {
@@ -35,10 +36,12 @@ struct PyrArgs {
   const int32_t* xofs; const int16_t* alpha; const int32_t* yofs; const int16_t* beta;
   int simd_end;
   int nframes;
-  // work units of the level (build_pyr_units): wave `u` of frame f takes
-  // units[mask_index[f] * unit_mstride + u]; unit_mstride == 0: one list for every frame
-  const PyrUnit* units; int nunits; int64_t unit_mstride;
-  const int32_t* mask_index; int nmasks;   // index clamped to [0, nmasks)
+  // waves of the level (pack_pyr_units) for groups of `gsize` frame slots: wave `u` of group g
+  // takes waves[group_mask[g] * wave_mstride + u]; wave_mstride == 0: one list for every group
+  const PyrWave* waves; int nwaves; int64_t wave_mstride;
+  // frames of group g: group_frames[g * gsize + slot], ascending, -1 = absent (k_pyr_groups);
+  // nullptr: the consecutive frames g * gsize + slot < nframes, and mask 0
+  const int32_t* group_frames; const int32_t* group_mask; int ngroups, gsize;
   // the full-frame geometry of pyr_strips (not read by the kernel)
   int tiles_x, tiles_y;            // tiles_x = column strips, tiles_y = row segments
   int core, seg_rows;              // strip width (px, multiple of 4, <= 244), segment height
@@ -50,6 +53,12 @@ inline void pyr_strips(int dw, int dh, int F, PyrArgs& a) {
 }
 // wide: source tiles for scale factors in (1.5, 2.2] (larger LDS footprint)
 void launch_pyr_blur(const PyrArgs& a, bool resize, bool wide, hipStream_t st);
+// group_frames / group_mask of a batch from its mask indices (pyr_groups.hpp), one workgroup.
+// Its counters are in LDS up to kPyrGroupMasks masks; beyond, in `scratch` (5 * nmasks entries)
+constexpr int kPyrGroupMasks = 256;
+void launch_pyr_groups(const int32_t* d_mask_index, int F, int nmasks, int G,
+                       int32_t* group_frames, int32_t* group_mask, int32_t* scratch,
+                       hipStream_t st);
 
 void launch_mask_pyramids(const Plan& pl, const uint8_t* d_masks, int n, uint8_t* dst,
                           hipStream_t st);

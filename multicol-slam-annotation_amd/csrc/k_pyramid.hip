@@ -7,15 +7,19 @@
 // downstream reads outside a level except the blur, which reflects explicitly here.
 #include "common.hpp"
 #include "extractor_kernels.hpp"
+#include "pyr_groups.hpp"
 #include "pyr_math.hpp"
 #include <type_traits>
 
 namespace mcs {
 
 // Row-streaming pyramid level: one wave owns a strip of `core` (<= 244) output columns and a
-// segment of rows, its PyrUnit from the frame's list (pyr_units.hpp: whole levels, or with
-// registered masks only what an output can depend on).  Lane L holds 4 consecutive pixels [xs-4+4L, xs+4L); lane 0 and
-// the lane after the core are the +-2 px halo of the blur.  A pixel outside the level holds
+// segment of rows, or two such strips ("runs") of the same segment in two frames of one mask
+// side by side, its PyrWave from its group's list (pyr_units.hpp: whole levels, or with
+// registered masks only what an output can depend on).  Lane L of a run holds 4 consecutive
+// pixels [xs-4+4L, xs+4L); the run's lane 0 and the lane after its core are the +-2 px halo of
+// the blur.  Only the column range, the x tables and a frame offset differ between the runs,
+// all per lane and set up before the row loop.  A pixel outside the level holds
 // the value of its BORDER_REFLECT_101 mirror (computed from the mirror's own coordinates),
 // so the horizontal 5-sum needs no border cases.  Rows are produced top to bottom with a
 // 2-row halo above and below the segment:
@@ -50,75 +54,124 @@ __global__ __launch_bounds__(256, MCS_PYR_OCC) void k_pyr_rows(PyrArgs a) {
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   uint32_t* const stage = lds_stage[wv];
   const uint8_t* const stb = reinterpret_cast<const uint8_t*>(stage);
-  int f, item;
-  if (!xcd_frame_map(blockIdx.x, a.nframes, (a.nunits + 3) / 4, &f, &item)) return;
+  int g, item;
+  if (!xcd_frame_map(blockIdx.x, a.ngroups, (a.nwaves + 3) / 4, &g, &item)) return;
   const int ui = item * 4 + wv;
-  if (ui >= a.nunits) return;
-  // the wave's unit (strip and row segment) from the frame's list: scalar loads, before any
-  // store (after one the compiler could no longer prove them unclobbered and would make them
-  // vector loads).  A pad unit (the shorter lists of other masks) has no rows.
-  const int mi = a.mask_index ? min(max(a.mask_index[f], 0), a.nmasks - 1) : 0;
-  // (read as two dwords: there is no scalar load of a 16-bit field)
-  static_assert(sizeof(PyrUnit) == 8 && alignof(PyrUnit) == 8, "PyrUnit is read as two dwords");
-  const uint2 uw = *reinterpret_cast<const uint2*>(a.units + ((int64_t)mi * a.unit_mstride + ui));
-  const int urows = (int)(int16_t)(uw.y >> 16);
+  if (ui >= a.nwaves) return;
+  // the wave's record (one or two runs of a row segment, pack_pyr_units) from its group's
+  // list and the frames of its runs: scalar loads, before any store (after one the compiler
+  // could no longer prove them unclobbered and would make them vector loads).  A pad wave (the
+  // shorter lists of other masks) has no rows.  Run A is r[0], run B r[1] in the lanes after it.
+  const int mi = a.group_mask ? a.group_mask[g] : 0;
+  // (read as four dwords: there is no scalar load of a 16-bit field)
+  static_assert(sizeof(PyrWave) == 16 && alignof(PyrWave) == 16, "PyrWave is read as four dwords");
+  const uint4 uw = *reinterpret_cast<const uint4*>(a.waves + ((int64_t)mi * a.wave_mstride + ui));
+  const int urows = (int)(int16_t)(uw.x >> 16);
   if (urows <= 0) return;
-  const int dw = a.dw, dh = a.dh, core = (int)(int16_t)(uw.x >> 16);
-  const int xs = (int)(int16_t)(uw.x & 0xFFFFu);
-  const int xcore1 = min(xs + core, dw);           // core px [xs, xcore1)
-  const int seg0 = (int)(int16_t)(uw.y & 0xFFFFu), seg1 = min(dh, seg0 + urows);
+  const int slot = (int)(int16_t)(uw.y & 0xFFFFu);
+  auto frame_of = [&](int s) -> int {
+    if (a.group_frames) return a.group_frames[(int64_t)g * a.gsize + s];
+    const int fr = g * a.gsize + s;
+    return fr < a.nframes ? fr : -1;
+  };
+  // frames fill a group's slots in order: without run A's frame there is none for run B
+  const int f = frame_of(slot);
+  if (f < 0) return;
+  const int fB = (uw.w >> 16) != 0 ? frame_of(slot + 1) : -1;
+  const bool two = fB >= 0;                        // an absent run B is dead lanes
+  const int dw = a.dw, dh = a.dh;
+  const int xsA = (int)(int16_t)(uw.z & 0xFFFFu), coreA = (int)(int16_t)(uw.z >> 16);
+  const int xsB = (int)(int16_t)(uw.w & 0xFFFFu), coreB = two ? (int)(int16_t)(uw.w >> 16) : 0;
+  const int seg0 = (int)(int16_t)(uw.x & 0xFFFFu), seg1 = min(dh, seg0 + urows);
   const int r_begin = max(0, seg0 - 2), r_end = min(dh, seg1 + 2);
-  const int xb = xs - 4 + 4 * lane;                // lane's first pixel
+  const int nA = coreA / 4 + 2;                    // run A's lanes: its core and a halo lane each side
+  const bool inB = two && lane >= nA;
+  const int xs = inB ? xsB : xsA, core = inB ? coreB : coreA;
+  const int xcore1 = min(xs + core, dw);           // core px [xs, xcore1) of the lane's run
+  const int xb = xs - 4 + 4 * (inB ? lane - nA : lane);   // lane's first pixel
   const bool core_lane = xb >= xs && xb < xcore1;
-  const uint8_t* S = a.src + (int64_t)f * a.src_fstride;
+  const uint8_t* S = a.src + (int64_t)f * a.src_fstride;  // run A's frame
   const int sh = RESIZE ? a.sh : dh;
 
-  // staged source columns [c_lo, c_hi]: the mirrors of the strip's pixels stay inside
-  // [xs-4, xs+core+4) clamped to the level; per pixel: the (mirrored) column it reads
-  int c_lo, c_hi;
+  // staged source columns [c_lo, c_hi] of each run: the mirrors of a run's pixels stay inside
+  // [xs-4, xs+core+4) clamped to the level.  With two runs both start at a multiple of 4, so
+  // that (frame strides being multiples of 4, pyr_level_packs) the bytes of both sit alike in
+  // their dwords and a row's byte shift is one value per wave.
+  int c_loA, c_hiA, c_loB = 0, c_hiB = 0;
+  if (RESIZE) {
+    c_loA = __builtin_amdgcn_readfirstlane(a.xofs[max(xsA - 4, 0)]);
+    c_hiA = min(__builtin_amdgcn_readfirstlane(a.xofs[min(xsA + coreA + 3, dw - 1)]) + 1, a.sw - 1);
+    if (two) {
+      c_loB = __builtin_amdgcn_readfirstlane(a.xofs[max(xsB - 4, 0)]) & ~3;
+      c_hiB = min(__builtin_amdgcn_readfirstlane(a.xofs[min(xsB + coreB + 3, dw - 1)]) + 1, a.sw - 1);
+    }
+  } else {
+    c_loA = max(xsA - 4, 0);
+    c_hiA = min(xsA + coreA + 3, dw - 1);
+    if (two) { c_loB = max(xsB - 4, 0) & ~3; c_hiB = min(xsB + coreB + 3, dw - 1); }
+  }
+  if (two) c_loA &= ~3;
+  const int nbytesA = c_hiA - c_loA + 1, nbytesB = c_hiB - c_loB + 1;
+  // run A's dwords of a staged row come first, run B's from dword ndwA on: A's count at the
+  // largest byte shift its rows can have (one value where the pitch is a multiple of 4)
+  const int shft_max = (a.spitch & 3) ? 3 : (int)((uintptr_t)(S + c_loA) & 3);
+  const int ndwA = two ? (shft_max + nbytesA + (RESIZE ? 1 : 0) + 3) >> 2 : NDW * 64;
+  // per pixel: the (mirrored) column it reads, as a byte of the staged row
+  const int c_lo = inB ? c_loB : c_loA, c_span = inB ? c_hiB - c_loB : c_hiA - c_loA;
+  const int stage_off = inB ? 4 * ndwA : 0;
   int sx[4];
   uint32_t aa[4];     // alpha0 | alpha1 << 16 (v_dot2_u32_u16 operand)
   int simd = 0;       // bit k: pixel k uses the SSE2 vertical form
   if (RESIZE) {
-    c_lo = __builtin_amdgcn_readfirstlane(a.xofs[max(xs - 4, 0)]);
-    c_hi = min(__builtin_amdgcn_readfirstlane(a.xofs[min(xs + core + 3, dw - 1)]) + 1, a.sw - 1);
 #pragma unroll
     for (int k = 0; k < 4; k++) {
       const int p = min(max(refl101(xb + k, dw), 0), dw - 1);
       // the right neighbour is read at sx + 1 even where resize clamps it to sx (the last
       // source column): alpha1 is 0 there, and sx + 1 stays inside the staged LDS row
-      sx[k] = min(max(a.xofs[p] - c_lo, 0), c_hi - c_lo);
+      sx[k] = min(max(a.xofs[p] - c_lo, 0), c_span) + stage_off;
       // alpha << 4 (alpha <= 2048, so <= 32768 still fits u16): the dot product is s << 4
       aa[k] = ((uint32_t)(uint16_t)a.alpha[2 * p] | ((uint32_t)(uint16_t)a.alpha[2 * p + 1] << 16)) << 4;
       simd |= (p < a.simd_end) << k;
     }
   } else {
-    c_lo = max(xs - 4, 0);
-    c_hi = min(xs + core + 3, dw - 1);
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-      sx[k] = min(max(min(max(refl101(xb + k, dw), 0), dw - 1) - c_lo, 0), c_hi - c_lo);
+      sx[k] = min(max(min(max(refl101(xb + k, dw), 0), dw - 1) - c_lo, 0), c_span) + stage_off;
       aa[k] = 0;
     }
   }
-  const int nbytes0 = c_hi - c_lo + 1;
 
-  // ---- streamed source rows: aligned dwords covering [c_lo, c_hi]
+  // ---- streamed source rows: aligned dwords covering [c_lo, c_hi] of each run
   auto row_base = [&](int sr) -> const uint8_t* { return S + (int64_t)sr * a.spitch; };
+  // Lane L loads dwords L + 64 m of the staged row.  Set up once, as byte offsets from run
+  // A's first dword: that of the lane's dword, and that of the last source byte of the
+  // dword's run before the row's byte shift.  Run B starts a multiple of 4 bytes after run A
+  // (a later frame: not negative, below 2^32 by the host's check).
+  uint32_t ld4[NDW], ldlast[NDW];
+#pragma unroll
+  for (int m = 0; m < NDW; m++) {
+    const int j = lane + 64 * m;
+    const bool ldB = two && j >= ndwA;
+    const uint32_t run = ldB ? (uint32_t)((int64_t)(fB - f) * a.src_fstride + (c_loB - c_loA)) : 0u;
+    ld4[m] = run + 4u * (uint32_t)(ldB ? j - ndwA : j);
+    ldlast[m] = run + (uint32_t)(ldB ? nbytesB : nbytesA) - 1u;
+  }
   // Every dword is loaded whole, also the last one of the last row of a frame buffer: an
   // aligned dword that holds a valid byte lies in that byte's page, so it cannot fault, and
-  // its bytes past the row end are never consumed.  No conditional tail: a register written
-  // on two paths would have to be merged, and that merge waits for every load in flight.
+  // its bytes past the row end are never consumed (a lane past its run's last such dword
+  // loads that one again).  No conditional tail: a register written on two paths would have
+  // to be merged, and that merge waits for every load in flight.
   auto load_row = [&](int sr, uint32_t (&v)[NDW]) {
-    const uint8_t* st = row_base(sr) + c_lo;
-    const uint32_t* ap = dev::align_down4(st);
-    const int ndw = ((int)((uintptr_t)st & 3) + nbytes0 + 3) >> 2;
+    const uint8_t* st = row_base(sr) + c_loA;
+    const uint8_t* ap = reinterpret_cast<const uint8_t*>(dev::align_down4(st));
+    const uint32_t shft = (uint32_t)((uintptr_t)st & 3);
 #pragma unroll
-    for (int m = 0; m < NDW; m++) v[m] = ap[min(lane + 64 * m, ndw - 1)];
+    for (int m = 0; m < NDW; m++)
+      v[m] = *reinterpret_cast<const uint32_t*>(ap + min(ld4[m], (shft + ldlast[m]) & ~3u));
   };
   // stage a row and read this lane's 4 (mirrored) source bytes / resized values
   auto stage_and_gather = [&](int sr, const uint32_t (&v)[NDW], int (&h)[4]) {
-    const int shft = (int)((uintptr_t)(row_base(sr) + c_lo) & 3);
+    const int shft = (int)((uintptr_t)(row_base(sr) + c_loA) & 3);
 #pragma unroll
     for (int m = 0; m < NDW; m++) stage[lane + 64 * m] = v[m];
     dev::wave_sync();
@@ -137,6 +190,10 @@ __global__ __launch_bounds__(256, MCS_PYR_OCC) void k_pyr_rows(PyrArgs a) {
   // ---- raw row -> store, horizontal 5-sums, 5-row window, blurred rows out
   uint8_t* const dstf = RESIZE ? a.dst + (int64_t)f * a.dst_fstride : nullptr;
   uint8_t* const blrf = a.blur + (int64_t)f * a.blur_fstride;
+  // the lane's byte offset on run A's (uniform) row base: its first pixel, and for run B the
+  // distance to its later frame
+  const uint32_t dst_off = (uint32_t)xb + (inB ? (uint32_t)((int64_t)(fB - f) * a.dst_fstride) : 0u);
+  const uint32_t blr_off = (uint32_t)xb + (inB ? (uint32_t)((int64_t)(fB - f) * a.blur_fstride) : 0u);
   uint32_t win[5][2];   // packed u16 5-sums of raw rows r-4..r (win[4] = newest)
 #pragma unroll
   for (int i = 0; i < 5; i++) win[i][0] = win[i][1] = 0;
@@ -148,7 +205,7 @@ __global__ __launch_bounds__(256, MCS_PYR_OCC) void k_pyr_rows(PyrArgs a) {
       const uint32_t q0 = (s01 & 0xFFFFu) * 671090u + 8388625u, q1 = (s01 >> 16) * 671090u + 8388625u;
       const uint32_t q2 = (s23 & 0xFFFFu) * 671090u + 8388625u, q3 = (s23 >> 16) * 671090u + 8388625u;
       const uint32_t o = __builtin_amdgcn_perm(q1, q0, 0x0C0C0703u) | __builtin_amdgcn_perm(q3, q2, 0x07030C0Cu);
-      *reinterpret_cast<uint32_t*>(dev::uniform_ptr(blrf + (int64_t)y * a.bpitch) + (uint32_t)xb) = o;
+      *reinterpret_cast<uint32_t*>(dev::uniform_ptr(blrf + (int64_t)y * a.bpitch) + blr_off) = o;
     }
   };
   // interior row y = r - 2 (2 <= y <= dh - 3): plain 5-row sum of the window
@@ -175,7 +232,7 @@ __global__ __launch_bounds__(256, MCS_PYR_OCC) void k_pyr_rows(PyrArgs a) {
   };
   auto push_row = [&](int r, uint32_t v) {
     if (RESIZE && core_lane && r >= seg0 && r < seg1)   // row base uniform, lane offset >= 0
-      *reinterpret_cast<uint32_t*>(dev::uniform_ptr(dstf + (int64_t)r * a.dpitch) + (uint32_t)xb) = v;
+      *reinterpret_cast<uint32_t*>(dev::uniform_ptr(dstf + (int64_t)r * a.dpitch) + dst_off) = v;
     // lane neighbours by DPP wave shifts (VALU, no LDS round trip); lane 0 / 63 read 0
     // (bound_ctrl), and those lanes are halo lanes whose blurred output is never stored
     const uint32_t L = (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x138 /*wave_shr:1*/, 0xF, 0xF, true);
@@ -332,14 +389,88 @@ __global__ __launch_bounds__(256, MCS_PYR_OCC) void k_pyr_rows(PyrArgs a) {
 }
 
 void launch_pyr_blur(const PyrArgs& a, bool resize, bool wide, hipStream_t st) {
-  if (a.nunits <= 0) return;   // no frame needs a pixel of this level
-  const unsigned g = xcd_grid(a.nframes, (a.nunits + 3) / 4);
+  if (a.nwaves <= 0 || a.ngroups <= 0) return;   // no frame needs a pixel of this level
+  const unsigned g = xcd_grid(a.ngroups, (a.nwaves + 3) / 4);
   if (!resize)
     hipLaunchKernelGGL((k_pyr_rows<false, 1>), dim3(g), dim3(256), 0, st, a);
   else if (!wide)
     hipLaunchKernelGGL((k_pyr_rows<true, 2>), dim3(g), dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL((k_pyr_rows<true, 3>), dim3(g), dim3(256), 0, st, a);
+}
+
+// ---------------------------------------------------------------------------
+// Which frames share a group of k_pyr_rows' waves: the rule that pyr_groups.hpp states serially
+// (a stable counting sort of the frames by clamped mask index, G to a group), worked by one
+// workgroup.  Per round of 256 frames a frame's rank among those of its mask is the mask's
+// count so far, the counts of the waves before its own and the frames of its mask in the lanes
+// below it.  The counters (nmasks + 4 nmasks) live in LDS up to kPyrGroupMasks masks and in a
+// scratch buffer of the extractor beyond; tests hold the result to the header's rule.
+// ---------------------------------------------------------------------------
+// next[m]: frames of mask m, then its next free entry; wcnt[w * nmasks + m]: frames of mask m
+// in wave w of the round
+__device__ __forceinline__ void pyr_groups_body(const int32_t* __restrict__ mask_index, int F,
+                                                int nmasks, int G, int32_t* __restrict__ group_frames,
+                                                int32_t* __restrict__ group_mask, int32_t* next,
+                                                int32_t* wcnt) {
+  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+  const int ng = pyr_groups_max(F, G, nmasks);
+  for (int i = tid; i < ng * G; i += 256) group_frames[i] = -1;
+  for (int i = tid; i < ng; i += 256) group_mask[i] = 0;
+  for (int t = tid; t < nmasks; t += 256) next[t] = 0;
+  __syncthreads();
+  for (int f = tid; f < F; f += 256) atomicAdd(&next[pyr_clamp_mask(mask_index[f], nmasks)], 1);
+  __syncthreads();
+  if (tid == 0) {
+    int first = 0;
+    for (int m = 0; m < nmasks; m++) {
+      const int n = pyr_groups_of(next[m], G);
+      for (int g = first; g < first + n; g++) group_mask[g] = m;
+      next[m] = first * G;
+      first += n;
+    }
+  }
+  __syncthreads();
+  for (int base = 0; base < F; base += 256) {
+    const int f = base + tid;
+    const int m = f < F ? pyr_clamp_mask(mask_index[f], nmasks) : -1;
+    int rank = 0;
+    for (int mm = 0; mm < nmasks; mm++) {
+      const uint64_t b = __ballot(m == mm);
+      if (m == mm) rank = __popcll(b & ((1ull << lane) - 1ull));
+      if (lane == 0) wcnt[wv * nmasks + mm] = __popcll(b);
+    }
+    __syncthreads();
+    if (m >= 0) {
+      int e = next[m] + rank;
+      for (int w = 0; w < wv; w++) e += wcnt[w * nmasks + m];
+      group_frames[e] = f;
+    }
+    __syncthreads();
+    for (int t = tid; t < nmasks; t += 256)
+      next[t] += wcnt[t] + wcnt[nmasks + t] + wcnt[2 * nmasks + t] + wcnt[3 * nmasks + t];
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(256) void k_pyr_groups(const int32_t* __restrict__ mask_index, int F,
+                                                    int nmasks, int G,
+                                                    int32_t* __restrict__ group_frames,
+                                                    int32_t* __restrict__ group_mask,
+                                                    int32_t* __restrict__ scratch) {
+  __shared__ int32_t next[kPyrGroupMasks], wcnt[4 * kPyrGroupMasks];
+  if (nmasks <= kPyrGroupMasks)
+    pyr_groups_body(mask_index, F, nmasks, G, group_frames, group_mask, next, wcnt);
+  else
+    pyr_groups_body(mask_index, F, nmasks, G, group_frames, group_mask, scratch, scratch + nmasks);
+}
+
+// scratch: 5 * nmasks entries, read only with more than kPyrGroupMasks masks
+void launch_pyr_groups(const int32_t* d_mask_index, int F, int nmasks, int G,
+                       int32_t* group_frames, int32_t* group_mask, int32_t* scratch,
+                       hipStream_t st) {
+  hipLaunchKernelGGL(k_pyr_groups, dim3(1), dim3(256), 0, st, d_mask_index, F, nmasks, G,
+                     group_frames, group_mask, scratch);
 }
 
 // ---------------------------------------------------------------------------

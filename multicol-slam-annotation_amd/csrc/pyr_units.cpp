@@ -145,4 +145,71 @@ void build_pyr_units(const Plan& pl, const PyrNeed* need, int F,
   }
 }
 
+namespace {
+
+// Dwords a run stages per source row at most (k_pyr_rows c_lo / c_hi; the resize reads one
+// byte past its last column).  Rows of a pitch that is no multiple of 4 start at any byte of a
+// dword; otherwise the frames are dword aligned and the shift is that of the first column.
+int run_stage_dw(const Plan& pl, int l, const PyrRun& r, bool two) {
+  const int w = pl.lv[l].w;
+  int c_lo, c_hi;
+  if (l) {
+    const int32_t* xofs = pl.xofs.data() + pl.xtab_off[l];
+    c_lo = xofs[std::max(r.x0 - 4, 0)];
+    c_hi = std::min(xofs[std::min(r.x0 + r.core + 3, w - 1)] + 1, pl.lv[l - 1].w - 1);
+  } else {
+    c_lo = std::max(r.x0 - 4, 0);
+    c_hi = std::min(r.x0 + r.core + 3, w - 1);
+  }
+  if (two) c_lo &= ~3;
+  const int shift = pyr_src_pitch(pl, l) % 4 == 0 ? (c_lo & 3) : 3;
+  return (shift + (c_hi - c_lo + 1) + (l ? 1 : 0) + 3) >> 2;
+}
+
+}  // namespace
+
+void pack_pyr_units(const Plan& pl, const std::vector<PyrUnit> (&lists)[kMaxLevels], int G,
+                    std::vector<PyrWave> (&waves)[kMaxLevels]) {
+  for (int l = 0; l < kMaxLevels; l++) waves[l].clear();
+  for (int l = 0; l < pl.nlevels; l++) {
+    const std::vector<PyrUnit>& in = lists[l];
+    const int w = pl.lv[l].w;
+    const bool packs = G > 1 && pyr_level_packs(pl, l);
+    const int max_dw = std::min(64 * pyr_stage_ndw(pl, l), kPyrStageDW);
+    for (size_t i = 0; i < in.size();) {
+      // the units of one row segment are consecutive: their span [lo, hi)
+      size_t j = i;
+      int lo = in[i].x0, hi = in[i].x0 + in[i].core;
+      for (; j < in.size() && in[j].row0 == in[i].row0 && in[j].rows == in[i].rows; j++) {
+        lo = std::min<int>(lo, in[j].x0);
+        hi = std::max<int>(hi, in[j].x0 + in[j].core);
+      }
+      const int len = (std::min(hi, w) - lo + 3) & ~3;
+      int s = 0, x = lo;
+      while (s < G) {
+        PyrWave wv{in[i].row0, in[i].rows, (int16_t)s, 0, {{0, 0}, {0, 0}}};
+        const int c0 = std::min(lo + len - x, kPyrMaxCore);
+        wv.r[0] = PyrRun{(int16_t)x, (int16_t)c0};
+        x += c0;
+        if (x >= lo + len) {
+          s++; x = lo;
+          if (packs && s < G) {
+            int c1 = std::min(len, kPyrMaxCore2 - c0) & ~3;
+            while (c1 > 0 && run_stage_dw(pl, l, wv.r[0], true) +
+                                 run_stage_dw(pl, l, PyrRun{(int16_t)lo, (int16_t)c1}, true) > max_dw)
+              c1 -= 4;
+            if (c1 > 0) {
+              wv.r[1] = PyrRun{(int16_t)lo, (int16_t)c1};
+              x = lo + c1;
+              if (c1 >= len) { s++; x = lo; }
+            }
+          }
+        }
+        waves[l].push_back(wv);
+      }
+      i = j;
+    }
+  }
+}
+
 }  // namespace mcs
