@@ -1,76 +1,22 @@
-// The BA edge math that is pinned against the reference text: the Cayley rotation, the
-// projection error of EdgeProjectXYZ2MCS and its analytic Jacobians, g2o's Huber kernel and the
-// 3x3 point-block algebra of BlockSolver<6,3> (same operation order as oracle/ba_oracle.cpp).
+// The BA edge math that is pinned against the reference text: the projection error of
+// EdgeProjectXYZ2MCS and its analytic Jacobians, g2o's Huber kernel and the 3x3 point-block
+// algebra of BlockSolver<6,3> (same operation order as oracle/ba_oracle.cpp).  The Cayley
+// rotation, M_t M_c, invMat, WorldToImg and the Horner polynomial are frm:: of omni_geom.hpp.
 // No device state: every function takes plain pointers, so another solver can include it.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "omni_geom.hpp"
 
 namespace mcs::ba {
-__device__ __forceinline__ void cay2rot(const double* c, double* R) {
-  const double c1 = c[0], c2 = c[1], c3 = c[2];
-  const double c1s = c1 * c1, c2s = c2 * c2, c3s = c3 * c3;
-  const double scale = 1 + c1s + c2s + c3s;
-  const double inv = 1 / scale;
-  R[0] = inv * (1 + c1s - c2s - c3s); R[1] = inv * (2 * (c1 * c2 - c3)); R[2] = inv * (2 * (c1 * c3 + c2));
-  R[3] = inv * (2 * (c1 * c2 + c3)); R[4] = inv * (1 - c1s + c2s - c3s); R[5] = inv * (2 * (c2 * c3 - c1));
-  R[6] = inv * (2 * (c1 * c3 - c2)); R[7] = inv * (2 * (c2 * c3 + c1)); R[8] = inv * (1 - c1s - c2s + c3s);
-}
-
-__device__ __forceinline__ double horner12(const double* a, double x) {
-  double r = 0.0;
-#pragma unroll
-  for (int i = 11; i >= 0; i--) r = r * x + a[i];
-  return r;
-}
-
-// err = meas - WorldToImg((M_t M_c)^-1 X): the reference's 4x4 path (computeError)
+// err = meas - WorldToImg((M_t M_c)^-1 X): the reference's 4x4 path (computeError), every
+// cv::Matx row from s = 0: M_t M_c, its invMat, the homogeneous product, WorldToImg
 __device__ void edge_error(const double* pose, const double* X, const double* mc,
                            const double* cam, const double* meas, double* err) {
-  double Rt[9], Rc[9];
-  cay2rot(pose, Rt);
-  cay2rot(mc, Rc);
-  // Mct = [Rt|tt][Rc|tc] (4x4 product, k = 0..3, last row 0 0 0 1)
-  double R[9], t[3];
-  for (int i = 0; i < 3; i++) {
-    for (int j = 0; j < 3; j++) {
-      double s = 0;
-      s += Rt[3 * i] * Rc[j];
-      s += Rt[3 * i + 1] * Rc[3 + j];
-      s += Rt[3 * i + 2] * Rc[6 + j];
-      s += pose[3 + i] * 0.0;
-      R[3 * i + j] = s;
-    }
-    double s = 0;
-    s += Rt[3 * i] * mc[3];
-    s += Rt[3 * i + 1] * mc[4];
-    s += Rt[3 * i + 2] * mc[5];
-    s += pose[3 + i] * 1.0;
-    t[i] = s;
-  }
-  // invMat: R' = R^T, t' = (-R') t ; X_c = R' X + t'
-  double ti[3];
-  for (int i = 0; i < 3; i++) {
-    double s = 0;
-    for (int k = 0; k < 3; k++) s += (-R[3 * k + i]) * t[k];
-    ti[i] = s;
-  }
-  double Xc[3];
-  for (int i = 0; i < 3; i++) {
-    double s = 0;
-    s += R[i] * X[0];
-    s += R[3 + i] * X[1];
-    s += R[6 + i] * X[2];
-    s += ti[i] * 1.0;
-    Xc[i] = s;
-  }
-  const double x = Xc[0], y = Xc[1], z = Xc[2];
-  double norm = sqrt(x * x + y * y);
-  if (norm == 0.0) norm = 1e-14;
-  const double theta = atan(-z / norm);
-  const double rho = horner12(cam + 5, theta);
-  const double uu = x / norm * rho, vv = y / norm * rho;
-  const double u = uu * cam[0] + vv * cam[1] + cam[3];
-  const double v = uu * cam[2] + vv + cam[4];
+  double R[9], t[3], Ri[9], ti[3], Xc[3], u, v;
+  frm::mtmc0(pose, mc, R, t);
+  frm::inv_rt(R, t, Ri, ti);
+  frm::hom_mul(Ri, ti, X, Xc);
+  frm::world_to_img(cam, Xc[0], Xc[1], Xc[2], u, v);
   err[0] = meas[0] - u;
   err[1] = meas[1] - v;
 }
@@ -91,12 +37,13 @@ __device__ void dcay(const double* c, int k, const double* R, double* D) {
     }
 }
 
-// analytic Jacobians of err: jp [2][6], jl [2][3]
+// analytic Jacobians of err: jp [2][6], jl [2][3].  X_c comes by the 3x3
+// path R^T (X - t), not edge_error's 4x4 path.
 __device__ void edge_jac(const double* pose, const double* X, const double* mc, const double* cam,
                          double* jp, double* jl) {
   double Rt[9], Rc[9], R[9];
-  cay2rot(pose, Rt);
-  cay2rot(mc, Rc);
+  frm::cay2rot(pose, Rt);
+  frm::cay2rot(mc, Rc);
   for (int i = 0; i < 3; i++)
     for (int j = 0; j < 3; j++) {
       double s = 0;
@@ -120,7 +67,7 @@ __device__ void edge_jac(const double* pose, const double* X, const double* mc, 
   if (rho == 0.0) rho = 1e-14;
   const double theta = atan(-z / rho);
   const double* a = cam + 5;
-  const double r = horner12(a, theta);
+  const double r = frm::horner(a, 12, theta);
   double dr = 0;
   for (int k = 11; k >= 1; k--) dr = dr * theta + k * a[k];
   const double den = rho * rho + z * z;

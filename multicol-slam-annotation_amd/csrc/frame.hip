@@ -6,13 +6,16 @@
 // WorldToImg :147-163, isPointInMirrorMask :165-180; cMultiCamSys_::WorldToCamHom_fast
 // src/cam_system_omni.cpp:92-112, Get_MtMc include/cam_system_omni.h:162-168;
 // cayley2rot include/misc.h:134-162, cConverter::invMat src/cConverter.cpp:31-44.
-// Compiled with -ffp-contract=off; double ops spelled with _rn intrinsics where an FMA could
-// otherwise be formed, so every rounding follows the reference's expression order.
-#include "proj_window.hpp"
+// The camera and pose math is omni_geom.hpp (this file's namespace).  Compiled with
+// -ffp-contract=off, so every rounding follows the reference's expression order.
+#include "common.hpp"
+#include "omni_geom.hpp"
 #include "../../include/mcs_frame.h"
 
 namespace mcs {
 namespace frm {
+
+constexpr int kGridCols = 64, kGridRows = 48;   // FRAME_GRID_COLS / ROWS (include/cMultiFrame.h:47-48)
 
 __global__ __launch_bounds__(256) void k_keypoint_rays(const mcs_keypoint* __restrict__ kps,
                                                        const int32_t* __restrict__ counts, int F,

@@ -15,8 +15,10 @@
 // GetFeaturesInArea, best Hamming distance.  The state-dependent tails (:1379-1415, :1536-1563,
 // :1692-1715) are mcs_fuse_select (fuse_select.cpp) on the host.
 // Compiled with -ffp-contract=off; every rounding follows the reference's expression order.
+// The projection and the epipolar check are frm:: of omni_geom.hpp.
 #include "host_util.hpp"
-#include "proj_window.hpp"
+#include "omni_geom.hpp"
+#include "window_walk.hpp"
 #include <algorithm>
 #include <climits>
 #include <vector>
@@ -62,13 +64,7 @@ __global__ __launch_bounds__(64) void k_fuse_setup(const double* __restrict__ m_
   if (rule != 0) return;
   double R1[9], t1[3], Ri[9], ti[3];
   frm::mtmc44(cur_mt, m_c + 16 * c, R1, t1);
-  for (int i = 0; i < 3; i++)   // invMat (cConverter.cpp:31-44): R' = R^T, t' = -R' t
-    for (int j = 0; j < 3; j++) Ri[3 * i + j] = R1[3 * j + i];
-  for (int i = 0; i < 3; i++) {
-    double s = 0.0;
-    for (int k = 0; k < 3; k++) s = __dadd_rn(s, __dmul_rn(-Ri[3 * i + k], t1[k]));
-    ti[i] = s;
-  }
+  frm::inv_rt(R1, t1, Ri, ti);   // Get_MtMc_inv
   double Rr[9], tr[3];   // Trel = T1 * T2, rows 0..2
   for (int i = 0; i < 3; i++) {
     for (int j = 0; j < 3; j++) {
@@ -117,7 +113,7 @@ __device__ __forceinline__ bool project(const Args& a, int t, int i, int c, doub
 }
 
 // One wave per (t, i, c).  Every lane computes the front half (it is wave-uniform); the window is
-// walked by win::walk_best (proj_window.hpp), whose wave minimum is the reference's first minimum
+// walked by win::walk_best (window_walk.hpp), whose wave minimum is the reference's first minimum
 // under strict <; use_dist = 0 is rule 1 as written, which never assigns dist (:1507-1514).
 // Offsets, cell ranges and cell entries are clamped to the target.
 __global__ __launch_bounds__(256) void k_fuse(Args a) {
@@ -147,8 +143,8 @@ __global__ __launch_bounds__(256) void k_fuse(Args a) {
       if (bd <= a.th_low) {
         bk = k;
         if (a.rule == 0 && a.epi_ok)
-          ep = epi_check(a.q_rays + 3 * (int64_t)i, a.rays + 3 * ((int64_t)o + k),
-                         a.E + 9 * ((int64_t)t * a.C + c), kEpiThresh) ? 1 : 0;
+          ep = frm::epi_check(a.q_rays + 3 * (int64_t)i, a.rays + 3 * ((int64_t)o + k),
+                              a.E + 9 * ((int64_t)t * a.C + c), kEpiThresh) ? 1 : 0;
       }
     }
   }

@@ -1,9 +1,13 @@
-// Descriptor distances shared by the matcher translation units (hamming.hip, bow_match.hip).
-// A descriptor row of W dwords (16, 32 or 64 bytes) is read with 16-byte vector loads.
+// Descriptor distances and tile sizes shared by the matcher translation units (hamming.hip,
+// tri_search.hip, bow_match.hip).  A descriptor row of W dwords (16, 32 or 64 bytes) is read with
+// 16-byte vector loads.
 #pragma once
 #include "common.hpp"
 
 namespace mcs {
+
+constexpr int kHamThreads = 256;
+constexpr int kHamTile = 256;      // train rows per LDS tile
 
 // DescriptorDistance64 (src/cORBmatcher.cpp:2443-2455)
 template <int W>

@@ -9,6 +9,7 @@
 #include "common.hpp"
 #include "desc_math.hpp"
 #include "extractor_kernels.hpp"
+#include "omni_geom.hpp"
 #include <algorithm>
 
 namespace mcs {
@@ -447,40 +448,11 @@ __global__ __launch_bounds__(64 * kDescWaves) void k_orient_desc(DescArgs a) {
 // dBRIEF / mdBRIEF (src/mdBRIEFextractorOct.cpp:250-283 rotateAndDistortPattern, :356-408
 // compute_dBRIEF, :410-554 compute_mdBRIEF; keypoint undistortion :1304-1316) on the
 // Scaramuzza model (src/cam_model_omni.cpp:49-163).  One wave per keypoint: every lane
-// distorts npoints/64 pattern points in double precision (ImgToWorld / WorldToImg with the
-// reference's operation order, no FMA), the pattern mean is summed by one lane in point
-// order (the reference's sequential sum), and the tests sample the padded level buffer the
-// reference reads (blurred ROI, raw reflect-101 border of 25 px, linear wrap beyond).
+// distorts npoints/64 pattern points in double precision (ImgToWorld / WorldToImg of
+// omni_geom.hpp: the reference's operation order, no FMA), the pattern mean is summed by one
+// lane in point order (the reference's sequential sum), and the tests sample the padded level
+// buffer the reference reads (blurred ROI, raw reflect-101 border of 25 px, linear wrap beyond).
 // ===========================================================================
-__device__ __forceinline__ double horner_d(const double* c, int s, double x) {
-  double r = 0.0;
-  for (int i = s - 1; i >= 0; i--) r = __dadd_rn(__dmul_rn(r, x), c[i]);
-  return r;
-}
-
-__device__ void img_to_world_d(const mcs_cam_model& m, double u, double v, double& x, double& y,
-                               double& z) {
-  const double invAffine = __dsub_rn(m.c, __dmul_rn(m.d, m.e));
-  const double u_t = __dsub_rn(u, m.u0), v_t = __dsub_rn(v, m.v0);
-  x = __ddiv_rn(__dsub_rn(u_t, __dmul_rn(m.d, v_t)), invAffine);
-  y = __ddiv_rn(__dadd_rn(__dmul_rn(-m.e, u_t), __dmul_rn(m.c, v_t)), invAffine);
-  const double X2 = __dmul_rn(x, x), Y2 = __dmul_rn(y, y);
-  z = -horner_d(m.p, m.p_deg, __dsqrt_rn(__dadd_rn(X2, Y2)));
-  const double norm = __dsqrt_rn(__dadd_rn(__dadd_rn(X2, Y2), __dmul_rn(z, z)));
-  x = __ddiv_rn(x, norm); y = __ddiv_rn(y, norm); z = __ddiv_rn(z, norm);
-}
-
-__device__ void world_to_img_d(const mcs_cam_model& m, double x, double y, double z, double& u,
-                               double& v) {
-  double norm = __dsqrt_rn(__dadd_rn(__dmul_rn(x, x), __dmul_rn(y, y)));
-  if (norm == 0.0) norm = 1e-14;
-  const double theta = atan(__ddiv_rn(-z, norm));
-  const double rho = horner_d(m.invp, m.invp_deg, theta);
-  const double uu = __dmul_rn(__ddiv_rn(x, norm), rho), vv = __dmul_rn(__ddiv_rn(y, norm), rho);
-  u = __dadd_rn(__dadd_rn(__dmul_rn(uu, m.c), __dmul_rn(vv, m.d)), m.u0);
-  v = __dadd_rn(__dadd_rn(__dmul_rn(uu, m.e), vv), m.v0);
-}
-
 __device__ __forceinline__ int refl101_d(int p, int n) {
   if (n == 1) return 0;
   while (p < 0 || p >= n) p = p < 0 ? -p : 2 * n - 2 - p;
@@ -551,10 +523,10 @@ __global__ __launch_bounds__(256) void k_dbrief(DescArgs a, int wave_lds) {
   if (a.do_dbrief) {
     const float fx = (l != 0) ? __fmul_rn((float)cx, L.scale) : (float)cx;
     const float fy = (l != 0) ? __fmul_rn((float)cy, L.scale) : (float)cy;
-    double x, y, z;
-    img_to_world_d(m, (double)fx, (double)fy, x, y, z);
-    ux = __dmul_rn(__ddiv_rn(-x, z), m.p[0]);
-    uy = __dmul_rn(__ddiv_rn(-y, z), m.p[0]);
+    double X[3];
+    frm::img_to_world(m, (double)fx, (double)fy, X);
+    ux = __dmul_rn(__ddiv_rn(-X[0], X[2]), m.p[0]);
+    uy = __dmul_rn(__ddiv_rn(-X[1], X[2]), m.p[0]);
   }
   // ---- rotateAndDistortPattern
   auto build = [&](double ang, int32_t* out) {
@@ -565,7 +537,7 @@ __global__ __launch_bounds__(256) void k_dbrief(DescArgs a, int wave_lds) {
       const double xr = __dadd_rn(__dsub_rn(__dmul_rn(px, ax), __dmul_rn(py, ay)), ux);
       const double yr = __dadd_rn(__dadd_rn(__dmul_rn(px, ay), __dmul_rn(py, ax)), uy);
       double u, v;
-      world_to_img_d(m, xr, yr, -m.p[0], u, v);
+      frm::world_to_img(m, xr, yr, -m.p[0], u, v);
       xs[p] = u;
       ys[p] = v;
     }

@@ -17,10 +17,11 @@
 // keypoint runs :277-364 and leaves a verdict, the point and the block's number of survivors.
 // k_np_admit: the survivors' output rows in idx1 order (ballot prefix in the wave, wave totals in
 // the block, the totals of the earlier blocks) and the admit step (:365-377).  Compiled with
-// -ffp-contract=off; cv::Matx products accumulate s = 0; s += a_k * b_k, k ascending.
+// -ffp-contract=off; cv::Matx products accumulate s = 0; s += a_k * b_k, k ascending.  M_t * M_c, its
+// invMat and WorldToImg are frm:: of omni_geom.hpp; the rows on a homogeneous (X, w) stay here.
 #include "host_util.hpp"
 #include "mappoint_math.hpp"
-#include "proj_window.hpp"
+#include "omni_geom.hpp"
 #include "../../include/mcs_newpoints.h"
 #include <climits>
 #include <cmath>
@@ -86,12 +87,7 @@ __device__ __forceinline__ void build_table(const Kf& k, int i1, int i2, double 
     for (int j = 0; j < 9; j++) d[j] = R[j];
 #pragma unroll
     for (int j = 0; j < 3; j++) d[9 + j] = t[j];
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-#pragma unroll
-      for (int j = 0; j < 3; j++) d[12 + 3 * i + j] = R[3 * j + i];
-      d[21 + i] = dot3(-R[i], -R[3 + i], -R[6 + i], t[0], t[1], t[2]);   // t' = -R' * t
-    }
+    frm::inv_rt(R, t, d + 12, d + 21);
   } else if (tid >= 64 && tid < 70) {          // GetCameraCenter: the translation of M_t
     const int j = tid - 64, kf = j / 3, r = j - 3 * kf;
     s_ow[j] = k.m_t[16 * (int64_t)(kf ? i2 : i1) + 4 * r + 3];
@@ -167,11 +163,10 @@ __device__ __forceinline__ int verdict(const double* T1, const double* T2, const
   const double c1 = __ddiv_rn(__dadd_rn(__dmul_rn(a1, l0), __dadd_rn(t1, __dmul_rn(f1, l1))), 2.0);
   const double c2 = __ddiv_rn(__dadd_rn(__dmul_rn(a2, l0), __dadd_rn(t2, __dmul_rn(f2, l1))), 2.0);
   // x3D4 = Tcw1 * (x3D, 1) (:315-317); the fourth row is 0 0 0 1
-  const double X0 = dot4(T1[0], T1[1], T1[2], T1[9], c0, c1, c2, 1.0);
-  const double X1 = dot4(T1[3], T1[4], T1[5], T1[10], c0, c1, c2, 1.0);
-  const double X2 = dot4(T1[6], T1[7], T1[8], T1[11], c0, c1, c2, 1.0);
+  const double c[3] = {c0, c1, c2};
+  frm::hom_mul(T1, T1 + 9, c, X);
+  const double X0 = X[0], X1 = X[1], X2 = X[2];
   const double w = dot4(0.0, 0.0, 0.0, 1.0, c0, c1, c2, 1.0);
-  X[0] = X0; X[1] = X1; X[2] = X2;
   double err;
   if (!reproject(T1 + 12, cam1, X0, X1, X2, w, k1x, k1y, &err)) return MCS_NP_BEHIND1;
   if (err > kMaxErr) return MCS_NP_REPROJ1;

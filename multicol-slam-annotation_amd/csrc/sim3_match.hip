@@ -11,11 +11,13 @@
 // Three launches: the transforms per candidate (:1729-1743 and the invMat(M_c) of :1795, :1889),
 // both projection passes (:1779-1967) with one wave per (candidate, direction, keypoint), and
 // the agreement check (:1969-1987).  Nothing depends on map state that changes during the call,
-// so there is no host tail.  The window walk is win::walk_best of proj_window.hpp, shared with
-// k_fuse.  Compiled with -ffp-contract=off; every rounding follows the reference's expression
-// order (cv::Matx products: s = 0; s += a_k * b_k, k ascending).
+// so there is no host tail.  The window walk is win::walk_best of window_walk.hpp, shared with
+// k_fuse; invMat, the Matx products and WorldToImg are frm:: of omni_geom.hpp.  Compiled with
+// -ffp-contract=off; every rounding follows the reference's expression order (cv::Matx products:
+// s = 0; s += a_k * b_k, k ascending).
 #include "host_util.hpp"
-#include "proj_window.hpp"
+#include "omni_geom.hpp"
+#include "window_walk.hpp"
 #include <algorithm>
 #include <climits>
 #include <vector>
@@ -98,15 +100,6 @@ __global__ __launch_bounds__(64) void k_sim3_setup(const double* __restrict__ mt
   n_found[idx] = 0;
 }
 
-// y = A * x + b: the Matx33d * Vec3d product (s = 0; s += a(i,k) x(k)), then the Vec sum
-__device__ __forceinline__ void rot_add(const double* A, const double* x, const double* b, double* y) {
-  for (int i = 0; i < 3; i++) {
-    double s = 0.0;
-    for (int k = 0; k < 3; k++) s = __dadd_rn(s, __dmul_rn(A[3 * i + k], x[k]));
-    y[i] = __dadd_rn(s, b[i]);
-  }
-}
-
 // One wave per (t, direction, keypoint): waves [0, T * n1) are direction 1 (:1779-1872), wave
 // T * n1 + j is direction 2 (:1874-1967) for keypoint j of the packed candidates.  Every lane
 // computes the front half (it is wave-uniform).  `from` is the keyframe whose map point is
@@ -161,18 +154,14 @@ __global__ __launch_bounds__(256) void k_sim3_search(Args a) {
     const double Pw[3] = {P[0], P[1], P[2]};
     double pa[3], pb[3], pc[3];
     if (d1) {
-      rot_add(a.T1, Pw, a.T1 + 9, pa);        // p3Dc1 = R1w * p3Dw + t1w
-      rot_add(xf + 21, pa, xf + 30, pb);      // p3Dc2 = sR21 * p3Dc1 + t21
+      frm::rot_add(a.T1, Pw, a.T1 + 9, pa);        // p3Dc1 = R1w * p3Dw + t1w
+      frm::rot_add(xf + 21, pa, xf + 30, pb);      // p3Dc2 = sR21 * p3Dc1 + t21
     } else {
-      rot_add(xf, Pw, xf + 9, pa);            // p3Dc2 = R2w * p3Dw + t2w
-      rot_add(xf + 12, pa, xf + 33, pb);      // p3Dc1 = sR12 * p3Dc2 + t12
+      frm::rot_add(xf, Pw, xf + 9, pa);            // p3Dc2 = R2w * p3Dw + t2w
+      frm::rot_add(xf + 12, pa, xf + 33, pb);      // p3Dc1 = sR12 * p3Dc2 + t12
     }
     const double* im = (d1 ? a.imc2 : a.imc1) + 12 * c;
-    for (int i = 0; i < 3; i++) {             // invMat(M_c) * toVec4d(p): k = 0..3
-      double s = 0.0;
-      for (int k = 0; k < 3; k++) s = __dadd_rn(s, __dmul_rn(im[3 * i + k], pb[k]));
-      pc[i] = __dadd_rn(s, __dmul_rn(im[9 + i], 1.0));
-    }
+    frm::hom_mul(im, im + 9, pb, pc);         // invMat(M_c) * toVec4d(p): k = 0..3
     double u = 0.0, v = 0.0, r = 0.0;
     int lv = 0, x0 = 0, x1 = 0, y0 = 0, y1 = 0;
     bool go = !(pb[2] < 0.0);                 // the depth test is on the rig-frame z (:1798, :1892)

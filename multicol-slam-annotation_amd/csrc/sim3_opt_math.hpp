@@ -3,10 +3,12 @@
 // conversions, the two edges of include/g2o_MultiCol_sim3_expmap.h:193-260, their analytic 2x7
 // Jacobians, the 7x7 solve and the two-round loop over g2o's LM control (lm_control.hpp).
 // k_sim3_opt (sim3_opt.hip) runs the same functions with the edges spread over a workgroup; its
-// control flow mirrors optimize_sim3_one below.  No HIP include: __host__ __device__ under hipcc,
-// inline under a host compiler.  Needs -ffp-contract=off.
+// control flow mirrors optimize_sim3_one below.  invMat, the homogeneous product and WorldToImg
+// are frm:: of omni_geom.hpp.  No HIP include: __host__ __device__ under hipcc, inline under a
+// host compiler.  Needs -ffp-contract=off.
 #pragma once
 #include "lm_control.hpp"
+#include "omni_geom.hpp"
 #include "../../include/mcs_matcher.h"
 #include <math.h>
 
@@ -179,39 +181,20 @@ MCS_LM_FN Sim3 sim3_inverse(const Sim3& a) {                           // sim3.h
 }
 
 // ---------------------------------------------------------------------------- the projection
-// invMat (src/cConverter.cpp:31-44) of a row-major 4x4 -> R [9], t [3]
-MCS_LM_FN void inv_mat44(const double* M, double* R, double* t) {
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) R[3 * i + j] = M[4 * j + i];
-  for (int i = 0; i < 3; i++) {
-    double s = 0.0;
-    for (int k = 0; k < 3; k++) s += -R[3 * i + k] * M[4 * k + 3];
-    t[i] = s;
-  }
-}
+// invMat of a row-major 4x4 and rows 0..2 of [R t; 0 0 0 1] * (x, 1): the shared definitions
+using frm::hom_mul;
+using frm::inv_mat44;
 
-// rows 0..2 of [R t; 0 0 0 1] * (x, 1) in cv::Matx order
-MCS_LM_FN void hom_mul(const double* R, const double* t, const double* x, double* y) {
-  for (int i = 0; i < 3; i++) {
-    double s = 0.0;
-    for (int k = 0; k < 3; k++) s += R[3 * i + k] * x[k];
-    y[i] = s + t[i] * 1.0;
-  }
-}
-
-// WorldToImg (src/cam_model_omni.cpp:147-163), cam = c d e u0 v0 invP[12]; with Jp the 2x3
+// WorldToImg (frm::world_to_img of omni_geom.hpp), cam = c d e u0 v0 invP[12]; with Jp the 2x3
 // derivative with respect to (x, y, z): the chain through norm, theta and the 12-term polynomial
-MCS_LM_FN void world_to_img(const double* cam, const double* p, double* uv, double* Jp) {
+MCS_LM_FN void world_to_img_jac(const double* cam, const double* p, double* uv, double* Jp) {
   const double x = p[0], y = p[1], z = p[2];
-  double n = sqrt(x * x + y * y);
+  double n = sqrt(x * x + y * y);   // the norm, theta and rho that WorldToImg forms and does not return
   if (n == 0.0) n = 1e-14;
   const double theta = atan(-z / n);
-  double rho = 0.0;
-  for (int i = 11; i >= 0; i--) rho = rho * theta + cam[5 + i];
+  const double rho = frm::horner(cam + 5, 12, theta);
   const double cx = x / n, cy = y / n;
-  const double uu = cx * rho, vv = cy * rho;
-  uv[0] = uu * cam[0] + vv * cam[1] + cam[3];
-  uv[1] = uu * cam[2] + vv + cam[4];
+  frm::world_to_img(cam, x, y, z, uv[0], uv[1]);
   if (!Jp) return;
   double drho = 0.0;
   for (int i = 11; i >= 1; i--) drho = drho * theta + i * cam[5 + i];
@@ -245,7 +228,7 @@ MCS_LM_FN void edge_eval(const Sim3& S, const Sim3& Si, const Row& r, int kind, 
   double Y[3], p[3], uv[2], Jp[6];
   sim3_map(kind ? Si : S, X, Y);
   hom_mul(imc + 12 * c, imc + 12 * c + 9, Y, p);
-  world_to_img(cam + 17 * c, p, uv, J ? Jp : nullptr);
+  world_to_img_jac(cam + 17 * c, p, uv, J ? Jp : nullptr);
   err[0] = obs[0] - uv[0];
   err[1] = obs[1] - uv[1];
   if (!J) return;

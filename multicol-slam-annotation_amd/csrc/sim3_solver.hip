@@ -17,10 +17,11 @@
 // form per (candidate, iteration)), k_s3s_check (CheckInliers, lanes over correspondences) and
 // k_s3s_resolve, which applies the sequential acceptance rule to the counts in iteration order.
 // Compiled with -ffp-contract=off; the prepare and check kernels follow the reference's
-// expression order (cv::Matx products: s = 0; s += a_k * b_k, k ascending).  cv::eigen and
-// cv::Rodrigues are OpenCV internals: the hypothesis is Horn's solution to rounding, not bitwise.
+// expression order (cv::Matx products: s = 0; s += a_k * b_k, k ascending) through frm:: of
+// omni_geom.hpp.  cv::eigen and cv::Rodrigues are OpenCV internals: the hypothesis is Horn's
+// solution to rounding, not bitwise.
 #include "host_util.hpp"
-#include "proj_window.hpp"
+#include "omni_geom.hpp"
 #include "sim3_draws.hpp"
 #include <algorithm>
 #include <cfloat>
@@ -61,24 +62,6 @@ struct Ransac {
 };
 
 struct Work { double* hyp; uint64_t* words; int32_t* inl; double* imc; };
-
-// y = A * x + b: the Matx33d * Vec3d product (s = 0; s += a(i,k) x(k)), then the Vec sum
-__device__ __forceinline__ void rot_add(const double* A, const double* x, const double* b, double* y) {
-  for (int i = 0; i < 3; i++) {
-    double s = 0.0;
-    for (int k = 0; k < 3; k++) s = __dadd_rn(s, __dmul_rn(A[3 * i + k], x[k]));
-    y[i] = __dadd_rn(s, b[i]);
-  }
-}
-
-// rows 0..2 of a 4x4 [A b; 0 0 0 1] times (x, 1): s = 0; s += a(i,k) x(k), k = 0..3
-__device__ __forceinline__ void hom_mul(const double* A, const double* b, const double* x, double* y) {
-  for (int i = 0; i < 3; i++) {
-    double s = 0.0;
-    for (int k = 0; k < 3; k++) s = __dadd_rn(s, __dmul_rn(A[3 * i + k], x[k]));
-    y[i] = __dadd_rn(s, __dmul_rn(b[i], 1.0));
-  }
-}
 
 // mvnMaxError1 / 2 are std::vector<size_t> (include/cSim3Solver.h:92-93): push_back(9.210 * sigma2)
 // truncates toward zero, and CheckInliers compares err < (double)that.  Values outside size_t's
@@ -154,13 +137,13 @@ __global__ __launch_bounds__(kPrep) void k_s3s_prepare(Set k1, Set k2, const dou
     frm::mtmc44(k1.m_t, k1.m_c + 16 * c1, R, tt);
     frm::world_to_cam_img(R, tt, k1.cam + 17 * c1, Xa, u, v);
     c.p1[2 * r] = u; c.p1[2 * r + 1] = v;
-    rot_add(s_h, Xa, s_h + 9, y);
+    frm::rot_add(s_h, Xa, s_h + 9, y);
     c.X1[3 * r] = y[0]; c.X1[3 * r + 1] = y[1]; c.X1[3 * r + 2] = y[2];
     c.cam1[r] = c1;
     frm::mtmc44(k2.m_t + 16 * (int64_t)t, k2.m_c + 16 * c2, R, tt);
     frm::world_to_cam_img(R, tt, k2.cam + 17 * c2, Xb, u, v);
     c.p2[2 * r] = u; c.p2[2 * r + 1] = v;
-    rot_add(s_h + 12, Xb, s_h + 21, y);
+    frm::rot_add(s_h + 12, Xb, s_h + 21, y);
     c.X2[3 * r] = y[0]; c.X2[3 * r + 1] = y[1]; c.X2[3 * r + 2] = y[2];
     c.cam2[r] = c2;
   }
@@ -402,10 +385,10 @@ __global__ __launch_bounds__(256) void k_s3s_check(Corr c, int n_it, Ransac r, W
             const double Xa[3] = {s_row[0][row], s_row[1][row], s_row[2][row]};
             const double Xb[3] = {s_row[3][row], s_row[4][row], s_row[5][row]};
             double p21[3], p12[3], q1[3], q2[3], u1, v1, u2, v2;
-            hom_mul(hy + 13, hy + 10, Xb, p21);            // pt2_in_1 = mT12i * X2
-            hom_mul(hy + 22, hy + 31, Xa, p12);            // pt1_in_2 = mT21i * X1
-            hom_mul(s_imc + 12 * ca, s_imc + 12 * ca + 9, p21, q1);
-            hom_mul(s_imc + 12 * cb, s_imc + 12 * cb + 9, p12, q2);
+            frm::hom_mul(hy + 13, hy + 10, Xb, p21);            // pt2_in_1 = mT12i * X2
+            frm::hom_mul(hy + 22, hy + 31, Xa, p12);            // pt1_in_2 = mT21i * X1
+            frm::hom_mul(s_imc + 12 * ca, s_imc + 12 * ca + 9, p21, q1);
+            frm::hom_mul(s_imc + 12 * cb, s_imc + 12 * cb + 9, p12, q2);
             frm::world_to_img(c.cam + 17 * ca, q1[0], q1[1], q1[2], u1, v1);
             frm::world_to_img(c.cam + 17 * cb, q2[0], q2[1], q2[2], u2, v2);
             const double d1x = __dsub_rn(s_row[6][row], u1), d1y = __dsub_rn(s_row[7][row], v1);

@@ -7,7 +7,7 @@
 // placing uses them too and a rank sort of every cell then restores ascending keypoint index,
 // the reference's push_back order, so the lists do not depend on scheduling.
 #pragma once
-#include "proj_window.hpp"
+#include "window_walk.hpp"
 
 namespace mcs {
 namespace trk {

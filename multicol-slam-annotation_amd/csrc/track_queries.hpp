@@ -4,12 +4,13 @@
 // Reference: SearchByProjection(F, vpMapPoints, th) src/cORBmatcher.cpp:67-166 with
 // RadiusByViewingCos; SearchByProjection(CurrentFrame, LastFrame, th) :1991-2123.  Rule 1
 // projects with the functions k_in_frustum uses (mtmc, world_to_cam_img, in_mirror_mask of
-// proj_window.hpp) on the same frame description; its projection is the window's centre and is
+// omni_geom.hpp) on the same frame description; its projection is the window's centre and is
 // held to the reference's bits, so WorldToImg's angle comes from atan_cr (correctly rounded:
 // equal to the host libm's atan except at the about 2.5 arguments in ten thousand the libm
 // misrounds, one ulp apart there) where k_in_frustum keeps the device library's atan: the two
 // can differ in the last place of a pixel coordinate.
 #pragma once
+#include "omni_geom.hpp"
 #include "track_grid.hpp"
 
 namespace mcs {

@@ -16,7 +16,7 @@
 // histograms.  GetFeaturesInArea's abs(kp.pt.x - x) is the double overload (the operand is a
 // double), i.e. fabs.
 #include "host_util.hpp"
-#include "proj_window.hpp"
+#include "window_walk.hpp"
 #include "../../include/mcs_matcher.h"
 #include <algorithm>
 #include <climits>
@@ -36,7 +36,7 @@ struct SearchArgs {
   int32_t* cand_ptr; int32_t* cand_kp; int32_t* cand_dist;
 };
 
-// One wave per query: win::window_candidates (proj_window.hpp), the grid taken as given.
+// One wave per query: win::window_candidates (window_walk.hpp), the grid taken as given.
 // COUNT: count only; else write (keypoint, distance) from cand_ptr[q].
 template <bool COUNT>
 __global__ __launch_bounds__(256) void k_window(SearchArgs a) {
