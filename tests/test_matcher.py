@@ -325,8 +325,10 @@ def _run_tri_device(ws, d1, d2, cam1, cam2, has1, has2, r1, r2, E, nbytes, th, t
 @pytest.mark.parametrize("seed,masked", [(0, False), (1, False), (2, True)])
 def test_triangulation_device_shared_candidates(gpu, seed, masked):
     """The device-resident entry on queries that compete for KF2 keypoints (the vbMatched2
-    greedy order matters) and on queries with more candidates than a slot holds, vs the oracle;
-    the host entry on the same input agrees too."""
+    greedy order matters) and on queries with more candidates in one train segment than its
+    slots hold (the rescan of the ordered pass), vs the oracle; the host entry on the same input
+    agrees too."""
+    from tests import tri_cases
     import mcs_amd
     nbytes = 32
     d1, d2, cam1, cam2, has1, has2, r1, r2, E = _tri_problem_shared(seed)
@@ -336,9 +338,10 @@ def test_triangulation_device_shared_candidates(gpu, seed, masked):
     thresh = 0.3
     nref, ref = _oracle_tri(d1, d2, cam1, cam2, has1, has2, r1, r2, E, thresh, m1, m2)
     assert nref > 50
-    # the problem really exercises both device paths: shared candidates and slot overflow
-    dist = np.unpackbits(d1[:4, None, :] ^ d2[None, :, :], axis=2).sum(2)
-    assert int(((dist <= th) & (cam2[None, :] == 0) & (has2[None, :] == 0)).sum(1).max()) > 64
+    # the problem really exercises both device paths: a (query, segment) over its slots, so
+    # every query goes to the ordered pass, and rescans there
+    reached, _ = tri_cases.paths(tri_cases.from_arrays(d1, d2, cam1, cam2, has1, has2, r1, r2, E, thresh, m1, m2))
+    assert reached["slot_overflow_pairs"] > 0 and reached["seq_rescan"] > 0
     L = mcs_amd.lib()
     ws = ctypes.c_void_p()
     assert L.mcs_tri_workspace_create(0, len(d1), len(d2), ctypes.byref(ws)) == 0
